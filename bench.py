@@ -26,6 +26,11 @@ SimpleRace).  N > 1: the env batch is sharded by global env id (weak scaling); `
 all-gather of (reward, game_over) per step; `screens_gather` / `c5` = secondary blocks, each under a watchdog phase
 (bench_lib/watchdog.py).  `--dry-run` prints the planned phases and their budgets without touching a GPU.
 
+`--dump-outputs DIR` (N = 1) writes what the loop hands its caller after its last step (bench_lib/dump.py), so that two builds
+can be compared output for output.  The timed regions start from a state the wall clock picks (spin, settle), so the step
+written is the last of one K-step region replayed, behind everything the line reports, from a checkpoint taken right after
+the warm-up: the same inputs on every run with the same arguments.
+
 Prints ONE JSON line (rank 0).  The parts live in bench_lib/ (workloads, plan, dist, loop, parity, watchdog, gather, c5, secondary).
 """
 import argparse
@@ -39,7 +44,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from bench_lib import gather, secondary, watchdog                                               # noqa: E402
+from bench_lib import dump, gather, secondary, watchdog                                         # noqa: E402
 from bench_lib.c5 import c5_block                                                               # noqa: E402
 from bench_lib.dist import init_distributed, library_comm                                       # noqa: E402
 from bench_lib.loop import Loop, region_trend                                                   # noqa: E402
@@ -84,6 +89,9 @@ def parse_args():
                     help="N > 1: seconds a secondary measurement may take before the watchdog prints the line without it; main gets 3x")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo exercises the code path)")
     ap.add_argument("--dry-run", action="store_true", help="print the planned phases and their watchdog budgets; touches no GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="N = 1: write what the timed loop's last step hands its caller as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB): the last step of one K-step region replayed from the state the warm-up left, which the arguments fix")
     return ap.parse_args()
 
 
@@ -97,6 +105,8 @@ def main():
         if rank == 0:
             print(json.dumps({"dry_run": True, "n_gpus": world, "workload": args.workload, "phases": plan(args, world)}))
         return
+    if args.dump_outputs and world > 1:
+        sys.exit("bench.py: --dump-outputs runs in one process (N = 1)")
     import torch
     import torch.distributed as dist
     from xworld_amd import sharding
@@ -151,6 +161,9 @@ def main():
     ceiling_buf = torch.empty(int(n_local * sim.obs_bytes_per_env), dtype=torch.uint8, device=dev)
     for _ in range(W):
         L.one_step()
+    # the last state reached after a number of steps the arguments fix: the spin and the settle regions below follow the wall clock
+    # (with the frames: a host copy of about 0.7 GB for xworld7, 2.8 GB for xworld7_f32, held until the replay has loaded it)
+    dump_from = sim.save_state() if args.dump_outputs else None
     # clocks warm, caches and allocator settled: spin by WALL TIME, every rank the same number of steps ...
     spun = 0
     t_end = time.perf_counter() + max(0.0, args.spin_seconds)
@@ -314,6 +327,18 @@ def main():
             line["parity"] = parity_gate(args.workload, L.rec, L.calls, slots, fused, 0, args.seed, min(args.parity_envs, n_local), probe_calls)
             if frames is not None:
                 line["parity"]["frames"] = frames
+        if args.dump_outputs:                            # behind the parity gate: the replay writes into the record it reads
+            sim.load_state(dump_from)
+            dump_from = None
+            for _ in range(K):
+                L.one_step()
+            L.fence()
+            assert sim.check_errors() == 0
+            # (load_state drops the lazy path's snapshots: the first steps after it run the classic path; a short K may end there)
+            dump_path = sim.step_path()
+            line["dump_outputs"] = {"dir": args.dump_outputs, "steps_after_warmup": K * fused, "path": dump_path,
+                                    "on_timed_path": dump_path["path"] == path_default["path"],
+                                    "arrays": dump.write_outputs(sim, L.rec[(L.calls - 1) % L.rec.shape[0]], args.dump_outputs)}
         if forced:
             line["forced_exchange"] = "world size 1: the N > 1 run's collectives were issued all the same (they move nothing between GPUs)"
         if not args.no_cpu_baseline and world == 1:      # rank 0, N = 1 only

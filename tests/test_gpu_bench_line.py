@@ -56,3 +56,45 @@ def test_driver_args_line_is_settled_and_complete():
     assert sec["xworld7_ego3"]["path"]["path"] == "ego_span" and sec["xworld7_ego3"]["value"] > 1.0e8
     assert sec["simple_game"]["one_launch"]["value"] > sec["simple_game"]["value"] > 2.0e9
     assert sec["simple_race"]["one_launch"]["value"] > sec["simple_race"]["value"] > 2.0e9
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_loops_and_do_not_follow_the_wall_clock(tmp_path):
+    """--dump-outputs: the last step of one K-step region from the state the warm-up left, whatever the spin and the settle
+    regions (which follow the wall clock) ran: two runs with different spins write the same arrays, and those are what the
+    loop computes in a batch of the same workload after 3 + 10 (bench.py's step-time probe) + W + K steps: the frames after the
+    last reset_done, reward and game_over code as that step computed them (before reset_done clears the finished envs' codes)."""
+    import numpy as np
+    import torch
+    lines, got = [], []
+    for spin in ("0", "0.2"):
+        out = str(tmp_path / ("spin" + spin))
+        lines.append(_line(["--repeats", "3", "--envs-per-gpu", "4096", "--no-parity", "--no-cpu-baseline", "--spin-seconds", spin,
+                            "--dump-outputs", out]))
+        got.append({f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))})
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) <= 64 * 10**6
+    d = lines[0]["dump_outputs"]
+    assert d["steps_after_warmup"] == 20 and d["path"]["path"] == lines[0]["path"]["path"] == "lazy_fused", (d, lines[0]["path"])
+    assert d["on_timed_path"]
+    a, b = got
+    assert set(a) == {"reward", "game_over", "actions", "obs", "obs_envs"} and {k: list(v.shape) for k, v in a.items()} == d["arrays"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    envs = a["obs_envs"].astype(np.int64)
+    assert 0 < len(envs) < 4096
+    from bench_lib.workloads import make_sim
+    sim = make_sim("xworld7", 4096, 0, 0)
+    ended = 0
+    for t in range(3 + 10 + 5 + 20):
+        sim.step()
+        if t >= 3 + 10 + 5:                            # the step's codes: reset_done clears those of the envs that finished
+            reward, codes = sim.reward.clone(), sim.game_over_codes.clone()
+            ended += int(codes.count_nonzero())
+        sim.reset_done()
+    torch.cuda.synchronize()
+    assert ended > 0
+    assert np.array_equal(a["reward"], reward.cpu().numpy()) and np.array_equal(a["game_over"], codes.cpu().numpy())
+    assert np.array_equal(a["actions"], sim.actions.cpu().numpy())
+    assert np.array_equal(a["obs"], sim.obs.cpu().numpy()[envs].astype(np.float32))
+    assert a["obs"].any()
+    sim.close()
