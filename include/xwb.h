@@ -424,6 +424,37 @@ int xwb_language_sentence(int32_t task, int32_t stage, int32_t event, const char
 int xwb_language_sentence_2d(int32_t task, int32_t timeup, const char *goal_name, const char *color, uint32_t seed, uint32_t gid,
                              uint32_t episode, uint32_t num_steps, char *out, size_t cap, size_t *need);
 
+/* ---- the teacher's sentences as word ids, for the whole batch on the device ----
+ * xwb_set_vocabulary: the vocabulary for xwb_sentence_ids -- words[i] gets id i (the reference's dict files, e.g.
+ * games/xworld/dicts/nav_2d.txt: one word per line, line = id; empty entries keep their id and match nothing).
+ * fold_case != 0: words are looked up ASCII-lower-cased, the vocabulary's as well (the reference's dicts are lower case; the
+ * grammars say "Could", "Well", "Time").  Words not in the vocabulary get unk_id (0 <= unk_id < n_words).  Duplicate words
+ * (after folding), a NULL word or n_words <= 0 -> XWB_ERR_ARG.  Every goal name, icon name and colour of xwb_set_names is
+ * looked up as ONE word: one that is empty or holds whitespace -> XWB_ERR_ARG (here, or from a later xwb_set_names).
+ * The words are copied; a later call replaces them.  XWorld2D batches only.  Synchronous (host tables + one upload).  The
+ * vocabulary is configuration, not state: xwb_save_state / xwb_load_state neither carry nor clear it. */
+int xwb_set_vocabulary(xwb_sim *sim, const char *const *words, int32_t n_words, int32_t unk_id, int32_t fold_case);
+/* Upper bound on the words of any sentence the batch's task groups can produce (a bound name or colour is one word; at least
+ * 1, the silent sentence).  For sizing max_len.  Needs no vocabulary. */
+int xwb_sentence_max_words(xwb_sim *sim, int32_t *n);
+/* The teacher's sentence of EVERY env after the last verb -- what xwb_sentence returns, word by word through the vocabulary --
+ * in one launch on `stream`, without synchronising: ids_dev[env * max_len + k] (int32[num_envs][max_len]; pad_id after the
+ * end), len_dev[env] = the sentence's full word count (int32[num_envs]; may exceed max_len: the row then holds the first
+ * max_len words).  A silent teacher ("" / the reference's "-"): silent_id >= 0 -> the one-word sentence silent_id,
+ * silent_id < 0 -> length 0.  Reads the live state the verbs queued on `stream` before it left (as xwb_get_env_state does).
+ * Needs xwb_set_names and xwb_set_vocabulary (else XWB_ERR_STATE); max_len >= 1. */
+int xwb_sentence_ids(xwb_sim *sim, int32_t *ids_dev, int32_t *len_dev, int32_t max_len, int32_t pad_id, int32_t silent_id,
+                     void *stream);
+/* The same expansion on the host, without a batch or a GPU (the twin of xwb_language_sentence / _2d for tests): the word ids
+ * of one sentence under a vocabulary.  Tasks 0-4 (and 6, 8: silent) take xwb_language_sentence's arguments; tasks 5 / 7 take
+ * xwb_language_sentence_2d's -- the target's name is goal_names[name_a], its colour `color` (task 7), num_steps the step count,
+ * event == 3 selects the "Time up ." message; stage, name_b and direction are unused.  Writes min(*need, cap) ids; *need = the
+ * sentence's word count (0: silent). */
+int xwb_language_sentence_ids(int32_t task, int32_t stage, int32_t event, const char *const *goal_names, int32_t n_goal_names,
+                              uint32_t name_a, uint32_t name_b, int32_t direction, const char *color, uint32_t seed, uint32_t gid,
+                              uint32_t episode, uint32_t num_steps, const char *const *words, int32_t n_words, int32_t unk_id,
+                              int32_t fold_case, int32_t *ids, int32_t cap, int32_t *need);
+
 /* SimulatorInterface::get_state(reward) of one env, serialised in the reference's StatePacket wire
  * layout (data_packet.h:313-319, data_packet.cpp:143-174, memory_util.h:307-333): keys "reward",
  * "screen" [, "sentence" for xworld].  Returns bytes needed in *need; writes when cap suffices.

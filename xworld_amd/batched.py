@@ -31,6 +31,16 @@ def _require(opts, key):
     return opts[key]
 
 
+_ASCII_LOWER = {c: c + 32 for c in range(ord("A"), ord("Z") + 1)}
+
+
+def read_vocabulary(path):
+    """The reference's dict format (games/xworld/dicts/*.txt): one word per line, stripped; line index = id.  Blank lines stay
+    entries (they match no word), so ids keep matching line numbers."""
+    with open(path, encoding="utf-8") as f:
+        return [ln.strip() for ln in f.read().splitlines()]
+
+
 class BatchedSimulator:
     def __init__(self, name, opts=None, num_envs=1, device=0, env_gid0=0, seed=0xC0FFEE, policy_seed=0x5EED):
         opts = dict(opts or {})
@@ -466,6 +476,61 @@ class BatchedSimulator:
         buf = C.create_string_buffer(need.value)
         lib.check(self.L.xwb_sentence(self.h, int(env), self._stream(stream), buf, need.value, C.byref(need)))
         return buf.value.decode()
+
+    def set_vocabulary(self, words_or_path, unk, fold_case=True):
+        """The vocabulary of sentence_ids(): a list of words (id = index) or the path of a dict file (read_vocabulary).  `unk`:
+        the id, or a word of the vocabulary, that words outside it get.  fold_case: look words up ASCII-lower-cased (the
+        reference's dicts are lower case, the grammars say "Could", "Well", "Time")."""
+        words = read_vocabulary(words_or_path) if isinstance(words_or_path, (str, os.PathLike)) else [str(w) for w in words_or_path]
+        fold = (lambda w: w.translate(_ASCII_LOWER)) if fold_case else (lambda w: w)
+        ids = {}
+        for i, w in enumerate(words):
+            if w:
+                ids.setdefault(fold(w), i)
+        if isinstance(unk, str):
+            if fold(unk) not in ids:
+                raise ValueError("unk word %r is not in the vocabulary" % unk)
+            unk = ids[fold(unk)]
+        enc = (C.c_char_p * len(words))(*[w.encode() for w in words])
+        lib.check(self.L.xwb_set_vocabulary(self.h, enc, len(words), int(unk), 1 if fold_case else 0))
+        self._vocab = (ids, int(unk), fold)
+
+    def sentence_max_words(self):
+        """Upper bound on the words of any sentence this batch's task groups can produce (the default max_len of sentence_ids)."""
+        n = C.c_int32()
+        lib.check(self.L.xwb_sentence_max_words(self.h, C.byref(n)))
+        return n.value
+
+    def sentence_ids(self, max_len=None, pad_id=0, silent="-", out=None, stream=None):
+        """The teacher's sentence of every env after the last verb as word ids, in one launch on the device and without a host
+        synchronisation: (ids int32[num_envs, max_len], lengths int32[num_envs]).  Row e holds the first max_len words of what
+        sentence(e) says, then pad_id; lengths[e] is the full word count.  A silent teacher says the word `silent` (looked up in the
+        vocabulary like any other word), or nothing when silent is None.  out=(ids, lengths) reuses the caller's tensors."""
+        import torch
+        if getattr(self, "_vocab", None) is None:
+            raise lib.XwbError("sentence_ids: set_vocabulary() has not been called")
+        max_len = self.sentence_max_words() if max_len is None else int(max_len)
+        if max_len < 1:
+            raise ValueError("max_len must be >= 1")
+        ids_of, unk, fold = self._vocab
+        silent_id = -1 if silent is None else ids_of.get(fold(silent), unk)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            ids = torch.empty((self.num_envs, max_len), dtype=torch.int32, device=dev)
+            lengths = torch.empty((self.num_envs,), dtype=torch.int32, device=dev)
+            if isinstance(stream, torch.cuda.Stream):          # the caching allocator hands these out for the current stream
+                ids.record_stream(stream)
+                lengths.record_stream(stream)
+        else:
+            ids, lengths = out
+            for t, shape in ((ids, (self.num_envs, max_len)), (lengths, (self.num_envs,))):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != shape \
+                        or not t.is_contiguous():
+                    raise ValueError("out: contiguous int32 tensors of shapes %s and %s on %s" % ((self.num_envs, max_len),
+                                                                                              (self.num_envs,), dev))
+        lib.check(self.L.xwb_sentence_ids(self.h, C.c_void_p(ids.data_ptr()), C.c_void_p(lengths.data_ptr()), max_len, int(pad_id),
+                                          int(silent_id), self._stream(stream)))
+        return ids, lengths
 
     def _group_sentence(self, env, stream, st, task, stage, event, target, steps_in_task):
         from . import language

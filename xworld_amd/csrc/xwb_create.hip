@@ -663,6 +663,7 @@ int xwb_destroy(xwb_sim *s) {
     if (!s) return XWB_OK;
     XWB_ON_DEVICE(s);
     for (void *p : s->allocs) (void)hipFree(p);
+    if (s->d_sent_tab) (void)hipFree(s->d_sent_tab);
     if (s->h_poison) (void)hipHostFree(s->h_poison);
     if (s->side) (void)hipStreamDestroy(s->side);
     if (s->ev_step) (void)hipEventDestroy(s->ev_step);

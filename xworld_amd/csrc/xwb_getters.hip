@@ -512,6 +512,7 @@ int xwb_set_names(xwb_sim *s, const char *const *goal_names, int32_t n_goal_name
     s->icon_names.assign(icon_names, icon_names + n_icons);
     s->icon_colors.assign(icon_colors, icon_colors + n_icons);
     s->have_names = true;
+    if (s->have_vocab) return sentence_tables_rebuild(s);     // the word ids of the bound names (xwb_sentence_ids)
     return XWB_OK;
 }
 

@@ -9,7 +9,10 @@
 // strings.  The rule texts, the stream and the order of the draws are those of language.py; tests/test_gpu_language_c.py
 // compares the two sentence for sentence, and language.py is pinned to the reference's CFG by tests/golden/sentences.json.
 #pragma once
+#include "xwb_sentence_ids.h"
+
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <sstream>
 #include <string>
@@ -261,6 +264,187 @@ inline std::string sentence_2d_timeup(int task) {
     Bindings b;
     b["S"] = "timeup";
     return g->expand(f, b);
+}
+
+// ---- word ids (xwb_set_vocabulary / xwb_sentence_ids): the rule texts above compiled into xwb_sentence_ids.h's flat tables ----
+
+inline std::string fold_ascii(std::string w) {
+    for (char &ch : w) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch - 'A' + 'a');
+    return w;
+}
+
+// words[i] -> i.  Empty entries (blank lines of a dict file) keep their ids and never match a word.
+struct Vocab {
+    std::map<std::string, int32_t> ids;
+    int32_t unk = 0;
+    bool fold = false;
+    int32_t id(const std::string &w) const {
+        const std::map<std::string, int32_t>::const_iterator it = ids.find(fold ? fold_ascii(w) : w);
+        return it == ids.end() ? unk : it->second;
+    }
+};
+
+// "" on success, else what is wrong
+inline std::string make_vocab(const char *const *words, int32_t n_words, int32_t unk, int32_t fold, Vocab &v) {
+    if (!words) return "words is NULL";
+    if (n_words <= 0 || n_words > sent::MAX_WORD_ID) return "n_words out of range";
+    if (unk < 0 || unk >= n_words) return "unk_id is not an id of the vocabulary";
+    v.ids.clear();
+    v.unk = unk;
+    v.fold = fold != 0;
+    for (int32_t i = 0; i < n_words; ++i) {
+        if (!words[i]) return "NULL word in the vocabulary";
+        if (!words[i][0]) continue;
+        const std::string w = v.fold ? fold_ascii(words[i]) : std::string(words[i]);
+        if (!v.ids.emplace(w, i).second) return "duplicate word in the vocabulary: '" + w + "'";
+    }
+    return "";
+}
+
+// the word id of a bound name / colour: the whole string is one word
+inline bool one_word(const std::string &s) {
+    if (s.empty()) return false;
+    for (char ch : s) if (ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\v' || ch == '\f') return false;
+    return true;
+}
+
+struct SentLayout {
+    std::vector<int32_t> tab;
+    sent::SentTab lay{};
+    int32_t max_words[sent::N_TASKS] = {};      // longest sentence per task (a bound name or colour is one word); 0: silent task
+};
+
+// the rules a task binds (language.py instruction_bindings / sentence_2d): those are slots, the others non-terminals
+inline int slot_of(int task, const std::string &sym) {
+    if (sym == "S") return sent::SL_S;
+    if (sym == "P" && task == 3) return sent::SL_P;
+    if (sym == "G" && task != 2 && task != 7) return sent::SL_G;
+    if (task == 2 && sym == "G1") return sent::SL_G1;
+    if (task == 2 && sym == "G2") return sent::SL_G2;
+    if (task == 7 && sym == "O") return sent::SL_O;
+    if (task == 7 && sym == "C") return sent::SL_C;
+    return -1;
+}
+
+// Builds the tables of every task with a grammar.  "" on success, else what is wrong.
+inline std::string compile_sentence_tables(const Vocab &v, const std::vector<std::string> &goal_names, const std::vector<std::string> &icon_names,
+                                           const std::vector<std::string> &icon_colors, SentLayout &out) {
+    using namespace sent;
+    for (const std::vector<std::string> *names : {&goal_names, &icon_names, &icon_colors})
+        for (const std::string &s : *names)
+            if (!one_word(s)) return "a name or colour is not one word: '" + s + "' (a bound name is one vocabulary entry)";
+    std::vector<int32_t> special(N_TASKS * N_SPECIAL, -1), nts, alts, syms;   // nts / alts: pairs (first, count)
+    std::vector<int32_t> nt_task;                                             // owning task of each non-terminal
+    static const char *const SPECIAL_NAMES[N_SPECIAL] = {"start", "correct", "wrong", "timeup", "finish", "FRONT", "BEHIND", "LEFT", "RIGHT"};
+    for (int task = 0; task < N_TASKS; ++task) {
+        const Grammar *g = grammar_of(task);
+        if (!g) continue;
+        std::map<std::string, int32_t> nt_id;
+        for (const auto &r : g->rules)
+            if (slot_of(task, r.first) < 0) { nt_id[r.first] = (int32_t)nt_task.size(); nt_task.push_back(task); }
+        nts.resize(2 * nt_task.size());
+        for (const auto &r : g->rules) {
+            const std::map<std::string, int32_t>::const_iterator self = nt_id.find(r.first);
+            if (self == nt_id.end()) continue;
+            nts[2 * self->second] = (int32_t)(alts.size() / 2);
+            nts[2 * self->second + 1] = (int32_t)r.second.size();
+            for (const std::vector<std::string> &alt : r.second) {
+                alts.push_back((int32_t)syms.size());
+                alts.push_back((int32_t)alt.size());
+                for (const std::string &s : alt) {
+                    if (s.size() >= 2 && s[0] == '\'') { syms.push_back(v.id(s.substr(1, s.size() - 2))); continue; }
+                    const int sl = slot_of(task, s);
+                    if (sl >= 0) { syms.push_back(SYM_SLOT | sl); continue; }
+                    const std::map<std::string, int32_t>::const_iterator it = nt_id.find(s);
+                    if (it == nt_id.end()) return "grammar of task " + std::to_string(task) + ": no rule for " + s;
+                    syms.push_back(SYM_NT | it->second);
+                }
+            }
+        }
+        for (int k = 0; k < N_SPECIAL; ++k) {
+            const std::map<std::string, int32_t>::const_iterator it = nt_id.find(SPECIAL_NAMES[k]);
+            if (it != nt_id.end()) special[task * N_SPECIAL + k] = it->second;
+        }
+    }
+    // longest sentence and deepest stack per symbol (the grammars are acyclic: a cycle is an error)
+    const int n_nt = (int)nt_task.size();
+    std::vector<int> words(n_nt, -1), depth(n_nt, -1), state(n_nt, 0);
+    std::string err;
+    std::function<void(int)> visit;
+    // words / stack entries a symbol of `task` expands to, at most; S and P: the largest rule they can be bound to (+1: the
+    // bound rule itself sits on the stack first)
+    std::function<void(int, int32_t, int &, int &)> cost = [&](int task, int32_t s, int &w, int &d) {
+        w = 1; d = 1;
+        if (s & SYM_NT) { visit(s & SYM_VALUE); w = words[s & SYM_VALUE]; d = depth[s & SYM_VALUE]; return; }
+        const int sl = s & SYM_VALUE;
+        if (!(s & SYM_SLOT) || (sl != SL_S && sl != SL_P)) return;
+        w = 0;
+        const int k0 = sl == SL_S ? SP_START : SP_FRONT, k1 = sl == SL_S ? SP_FINISH : SP_RIGHT;
+        for (int k = k0; k <= k1; ++k) {
+            const int32_t nt = special[task * N_SPECIAL + k];
+            if (nt < 0) continue;
+            visit(nt);
+            if (words[nt] > w) w = words[nt];
+            if (depth[nt] > d) d = depth[nt];
+        }
+    };
+    visit = [&](int nt) {
+        if (state[nt] == 2 || !err.empty()) return;
+        if (state[nt] == 1) { err = "cyclic grammar"; return; }
+        state[nt] = 1;
+        int wmax = 0, dmax = 1;
+        for (int32_t a = nts[2 * nt]; a < nts[2 * nt] + nts[2 * nt + 1]; ++a) {
+            const int32_t s0 = alts[2 * a], len = alts[2 * a + 1];
+            int wsum = 0;
+            for (int32_t i = 0; i < len; ++i) {
+                int w = 0, d = 1;
+                cost(nt_task[nt], syms[s0 + i], w, d);
+                wsum += w;
+                if ((len - 1 - i) + d > dmax) dmax = (len - 1 - i) + d;
+            }
+            if (wsum > wmax) wmax = wsum;
+        }
+        words[nt] = wmax; depth[nt] = dmax; state[nt] = 2;
+    };
+    for (int task = 0; task < N_TASKS; ++task) {
+        if (special[task * N_SPECIAL + SP_START] < 0) continue;
+        int w = 0, d = 1;
+        cost(task, SYM_SLOT | SL_S, w, d);              // the sentence starts from S (bound)
+        if (!err.empty()) return err;
+        if (d + 1 > STACK_MAX) return "grammar of task " + std::to_string(task) + " needs a deeper stack than STACK_MAX";
+        out.max_words[task] = w;
+    }
+    SentTab &L = out.lay;
+    L.n_nt = n_nt; L.n_alt = (int32_t)(alts.size() / 2); L.n_sym = (int32_t)syms.size();
+    L.n_goal = (int32_t)goal_names.size(); L.n_icon = (int32_t)icon_names.size();
+    L.off_nt = N_TASKS * N_SPECIAL;
+    L.off_alt = L.off_nt + (int32_t)nts.size();
+    L.off_sym = L.off_alt + (int32_t)alts.size();
+    L.off_goal = L.off_sym + L.n_sym;
+    L.off_iname = L.off_goal + L.n_goal;
+    L.off_icolor = L.off_iname + L.n_icon;
+    L.total = L.off_icolor + L.n_icon;
+    std::vector<int32_t> &t = out.tab;
+    t.assign(special.begin(), special.end());
+    t.insert(t.end(), nts.begin(), nts.end());
+    t.insert(t.end(), alts.begin(), alts.end());
+    t.insert(t.end(), syms.begin(), syms.end());
+    for (const std::string &s : goal_names) t.push_back(v.id(s));
+    for (const std::string &s : icon_names) t.push_back(v.id(s));
+    for (int i = 0; i < L.n_icon; ++i) t.push_back(v.id(i < (int)icon_colors.size() ? icon_colors[i] : std::string("na")));
+    L.t = nullptr;
+    return "";
+}
+
+// the longest sentence a task can produce (bound names one word each): the tables' structure does not depend on the words
+inline int32_t max_sentence_words(int task) {
+    static const SentLayout layout = [] {
+        SentLayout l;
+        Vocab v;
+        (void)compile_sentence_tables(v, {}, {}, {}, l);
+        return l;
+    }();
+    return task >= 0 && task < sent::N_TASKS ? layout.max_words[task] : 0;
 }
 
 }  // namespace lang

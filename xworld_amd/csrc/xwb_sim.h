@@ -9,6 +9,7 @@
 #include "../../include/xwb.h"
 #include "../../include/xwb_testing.h"
 #include "xwb_common.h"
+#include "xwb_sentence_ids.h"
 
 #include <cmath>
 #include <cstdio>
@@ -172,6 +173,14 @@ struct xwb_sim {
     // xwb_set_names: the strings behind the name ids (the teacher's sentences are built from them)
     std::vector<std::string> goal_names, icon_names, icon_colors;
     bool have_names = false;
+    // xwb_set_vocabulary / xwb_sentence_ids (xwb_sentence_ids.hip): the caller's words, and the grammar tables compiled with them
+    // and with the names above, uploaded to d_sent_tab (rebuilt when either changes)
+    std::vector<std::string> vocab_words;
+    int32_t vocab_unk = 0, vocab_fold = 0;
+    bool have_vocab = false, sent_tab_ok = false;
+    int32_t *d_sent_tab = nullptr;
+    size_t sent_tab_cap = 0;
+    xwb::sent::SentTab sent_lay{};
     xwb::XwParams xw{};
     std::vector<void *> allocs;
 };
@@ -218,6 +227,10 @@ int join_regen(xwb_sim *s, hipStream_t st);
 int launch_regen(xwb_sim *s, bool by_epoch);
 int flush_regen(xwb_sim *s);
 int xw_reset_list(xwb_sim *s, int mode, bool keep_done, bool render, hipStream_t st, bool beside_render = false);
+
+// ---- xwb_sentence_ids.hip ----
+// compiles the word-id tables from the vocabulary and the names and uploads them (synchronises the device); both must be set
+int sentence_tables_rebuild(xwb_sim *s);
 
 }  // namespace host
 }  // namespace xwb
