@@ -79,3 +79,66 @@ def test_resume_without_obs_and_config_check():
         c.load_state(small[:100])
     for s in (a, b, c):
         s.close()
+
+
+def _same(torch, a, b, where):
+    torch.cuda.synchronize()
+    for key in ("obs", "reward", "game_over_codes", "num_steps", "episode", "grid"):
+        assert torch.equal(getattr(a, key), getattr(b, key)), (where, key)
+
+
+def test_load_between_fused_step_and_reset_done():
+    """A blob saved between a one-launch step and its reset_done, loaded right away: the reset_done that follows must not wait
+    for the step's hand-over (nothing of that step is pending after a load), and the batch goes on as one on the classic path."""
+    import torch
+    from xworld_amd.batched import BatchedSimulator
+    n = 1024
+    a = BatchedSimulator("xworld", dict(NAV, color=True), num_envs=n, seed=3, policy_seed=4)
+    b = BatchedSimulator("xworld", dict(NAV, color=True, debug=["no_fused", "no_pregen"]), num_envs=n, seed=3, policy_seed=4)
+    for s in (a, b):
+        s.reset()
+        for _ in range(6):
+            s.step()
+            s.reset_done()
+        s.step()
+    assert a.step_path()["path"] == "lazy_fused" and b.step_path()["path"] == "classic"
+    for s in (a, b):
+        s.load_state(s.save_state())
+        s.reset_done()
+        assert s.check_errors() == 0                                          # (a poisoned batch raises here)
+    assert a.step_path()["path"] == "lazy_fused"
+    _same(torch, a, b, "after reset_done")
+    for t in range(8):
+        for s in (a, b):
+            s.step()
+            s.reset_done()
+        _same(torch, a, b, t)
+    assert a.check_errors() == b.check_errors() == 0
+    a.close()
+    b.close()
+
+
+def test_refused_load_leaves_the_batch_alone():
+    """A truncated blob is refused, and the batch that refused it keeps stepping exactly as a twin that never saw it."""
+    import torch
+    from xworld_amd.batched import BatchedSimulator
+    from xworld_amd.lib import XwbError
+    n = 1024
+    a, b = (BatchedSimulator("xworld", dict(NAV, color=True), num_envs=n, seed=8, policy_seed=2) for _ in range(2))
+    for s in (a, b):
+        s.reset()
+        for _ in range(5):
+            s.step()
+            s.reset_done()
+        s.step()                                                              # (the done list rotation is mid-way)
+    blob = a.save_state()
+    with pytest.raises(XwbError):
+        a.load_state(blob[:blob.size - 100])
+    for t in range(10):
+        for s in (a, b):
+            s.reset_done()
+            s.step()
+        _same(torch, a, b, t)
+    assert a.check_errors() == b.check_errors() == 0
+    a.close()
+    b.close()

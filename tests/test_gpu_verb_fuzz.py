@@ -20,7 +20,10 @@ CASES = {
                         "tasks": ["XWorld3DNavTarget", "XWorld3DNavTargetNear", "XWorld3DNavTargetBetween", "XWorld3DNavTargetDirection", "XWorld3DNavTargetAvoid"],
                         "tasks2": ["XWorldNavTarget", "XWorldNavNear", "XWorldNavColorTarget", "XWorldNavBetween"]},
     "ctx2": {"xwd_conf_path": NAV, "task_mode": "lang_acquisition", "max_dim": 7, "color": True, "context": 2, "max_steps": 20},     # (a context ring: no one-launch step)
+    # egocentric: the span path (front kernels, list gathers and the map generator on two queues) against the per-env render
+    "ego3": {"xwd_conf_path": NAV, "task_mode": "lang_acquisition", "max_dim": 7, "color": True, "visible_radius": 3, "max_steps": 25},
 }
+TWIN_DEBUG = {"ego3": ["ego_no_span"]}                              # (default: the classic kernel sequence)
 
 
 def _same(torch, a, b, where):
@@ -31,14 +34,15 @@ def _same(torch, a, b, where):
     assert torch.equal(a.grid, b.grid), where
 
 
-@pytest.mark.parametrize("case,seed", [("c4", 1), ("c4", 2), ("nav11_gray", 3), ("nav8_two_groups", 4), ("ctx2", 5)])
+@pytest.mark.parametrize("case,seed", [("c4", 1), ("c4", 2), ("nav11_gray", 3), ("nav8_two_groups", 4), ("ctx2", 5), ("ego3", 6)])
 def test_random_verb_sequences_default_paths_equal_classic(case, seed):
     import torch
     assert torch.cuda.is_available()
     from xworld_amd.batched import BatchedSimulator
     n = 1500
     a = BatchedSimulator("xworld", CASES[case], num_envs=n, seed=40 + seed, policy_seed=seed)
-    b = BatchedSimulator("xworld", dict(CASES[case], debug=["no_fused", "no_pregen"]), num_envs=n, seed=40 + seed, policy_seed=seed)
+    b = BatchedSimulator("xworld", dict(CASES[case], debug=TWIN_DEBUG.get(case, ["no_fused", "no_pregen"])), num_envs=n, seed=40 + seed,
+                         policy_seed=seed)
     rng = np.random.default_rng(seed)
     g = torch.Generator(device="cuda").manual_seed(seed)
     side = torch.cuda.Stream()
@@ -95,7 +99,10 @@ def test_random_verb_sequences_default_paths_equal_classic(case, seed):
             b.step(); b.reset_done()
         paths.add(a.step_path()["path"])
         _same(torch, a, b, (t, op, log[-6:]))
-    assert ("lazy_fused" in paths) == (case != "ctx2") and "lazy" in paths
+    if case == "ego3":
+        assert "ego_span" in paths and paths <= {"none", "ego_span"} and b.step_path()["path"] == "ego_per_env"
+    else:
+        assert ("lazy_fused" in paths) == (case != "ctx2") and "lazy" in paths
     # illegal ids were counted the same on both
     assert a.check_errors() == b.check_errors()
     a.close(); b.close()

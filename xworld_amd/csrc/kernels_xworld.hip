@@ -348,7 +348,7 @@ __device__ __forceinline__ void xw_step_body(const XwParams &p, const int blk, c
     if (e == 0) {
         // (pre-generated episodes: the regeneration of the previous step's list may still be reading that list and its count --
         // the counter zeroed here is the one it read, two steps back in the rotation)
-        if (p.swap_shadow) xw_wait_epoch_lane(p.sync + 8, p.regen_wait, p.sync + 4, p.poison_host);
+        if (p.swap_shadow) xw_wait_epoch_lane(p.sync + SYNC_REGEN, p.regen_wait, p.sync + SYNC_POISON, p.poison_host);
         *p.done_count_next = 0;                // double-buffered done counter: zero the next step's
     }
     bool is_done = false, idle3d = false;
@@ -408,7 +408,7 @@ __device__ __forceinline__ void xw_step_body(const XwParams &p, const int blk, c
         // a plain step whose reset_done will install pre-generated episodes (list_swap): nothing to install here, but the list
         // appended below may still be read by the previous step's regeneration
         if (__ballot(is_done)) {
-            if ((threadIdx.x & 63) == 0) xw_wait_epoch_lane(p.sync + 8, p.regen_wait, p.sync + 4, p.poison_host);
+            if ((threadIdx.x & 63) == 0) xw_wait_epoch_lane(p.sync + SYNC_REGEN, p.regen_wait, p.sync + SYNC_POISON, p.poison_host);
             __builtin_amdgcn_wave_barrier();
         }
     }
@@ -421,7 +421,7 @@ __device__ __forceinline__ void xw_step_body(const XwParams &p, const int blk, c
         const unsigned long long m = __ballot(is_done);
         if (m) {
             const int lane = threadIdx.x & 63, cells = p.max_dim * p.max_dim;
-            if (lane == __ffsll((long long)m) - 1) xw_wait_epoch_lane(p.sync + 8, p.regen_wait, p.sync + 4, p.poison_host);
+            if (lane == __ffsll((long long)m) - 1) xw_wait_epoch_lane(p.sync + SYNC_REGEN, p.regen_wait, p.sync + SYNC_POISON, p.poison_host);
             __builtin_amdgcn_wave_barrier();
             const uint32_t ep_old = is_done ? p.episode[e] : 0u;
             const int slot = (int)((ep_old + 1u) & 1u);                                  // the shadow slot that holds episode + 1
@@ -669,7 +669,7 @@ __global__ __launch_bounds__(BS) void xw_render_all_kernel(XwParams p) {
     __shared__ uint16_t s_code[L::CODES];
     __shared__ uint8_t s_done[L::NE];
     // this kernel running = the step kernel queued before it is complete: tell the reset kernel's queue (xw_device.h)
-    if (p.sig_epoch && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + 1, p.sig_epoch);
+    if (p.sig_epoch && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + SYNC_STEP, p.sig_epoch);
     if (p.no_draw) return;                                 // (xwb_xw_set_draw(sim, 0): launched with one workgroup, for the epoch)
     xw_render_span<DIM_T, CH, CTX1, BS, PER, RMODE, ES, false>(p, blockIdx.x, s_out4, s_code, s_done);
 }
@@ -717,7 +717,7 @@ __global__ __launch_bounds__(256) void xw_render_list_kernel(XwParams p, const i
     SP_T(1, 0);
     // (after a fused step + render launch this kernel is the first one behind the step in the caller's queue: it tells the
     // internal queue, whose regeneration pass reads the done list, that the step is complete)
-    if (p.sig_epoch && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + 1, p.sig_epoch);
+    if (p.sig_epoch && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + SYNC_STEP, p.sig_epoch);
     const int cnt = *count_now;
     const int i_first = (int)blockIdx.x / parts;
     const int e_first = p.done_list[i_first < p.n ? i_first : 0];
@@ -730,7 +730,7 @@ __global__ __launch_bounds__(256) void xw_render_list_kernel(XwParams p, const i
     // the kernels that publish the epoch need wave slots of their own.  render_list() therefore launches at most half the
     // machine's wave slots when a wait is attached (a batch whose envs all finish on one step otherwise parks one spinning
     // workgroup in every slot: seen as a 4 s stall on the 8x8 workload, where many envs time out on the same step).
-    if (p.wait_epoch) xw_wait_epoch(p.sync + p.wait_slot, p.wait_epoch, p.sync + 4, p.poison_host);
+    if (p.wait_epoch) xw_wait_epoch(p.sync + p.wait_slot, p.wait_epoch, p.sync + SYNC_POISON, p.poison_host);
     for (long long b = blockIdx.x; b < items; b += gridDim.x) {
         const int i = (int)(b / parts), part = (int)(b - (long long)i * parts);
         const bool first = b == (long long)blockIdx.x;
@@ -787,7 +787,7 @@ __global__ __launch_bounds__(256) void xw_render_list_kernel(XwParams p, const i
         SP_T(1, 3);
         if (c0 < hi) xw_store_chunk(frame0, c0, cpf, ctx, p.list_flag, v0);
         if (c1 < hi) xw_store_chunk(frame0, c1, cpf, ctx, p.list_flag, v1);
-        if (part == 0 && threadIdx.x == 0 && p.list_flag == 2) { p.fresh[e] = 0; if (p.auto_reset == 2) p.done[e] = 0; }
+        if (part == 0 && threadIdx.x == 0 && p.list_flag == 2) { p.fresh[e] = 0; if (p.auto_reset == AUTO_RESET_BY_LIST) p.done[e] = 0; }
         SP_T(1, 4);
     }
 }
@@ -843,36 +843,36 @@ static hipError_t render_list(const XwParams &p, hipStream_t s) {
 }
 
 template <int CH, int ES>
-static hipError_t render_dispatch(const XwParams &p, int indexed, hipStream_t s) {
-#define XW_CASE(DIMV) case DIMV: return indexed == 1 ? render_list<DIMV, CH, ES>(p, s) : (indexed == 2 ? render_all<DIMV, CH, 2, ES>(p, s) : (indexed == 3 ? render_all<DIMV, CH, 3, ES>(p, s) : render_all<DIMV, CH, 0, ES>(p, s)));
+// (render_all's RMODE: 0 every env, 2 RENDER_ALIVE, 3 RENDER_ALL_TERM)
+static hipError_t render_dispatch(const XwParams &p, RenderMode m, hipStream_t s) {
+#define XW_CASE(DIMV) case DIMV: return m == RENDER_LIST ? render_list<DIMV, CH, ES>(p, s) : (m == RENDER_ALIVE ? render_all<DIMV, CH, 2, ES>(p, s) : (m == RENDER_ALL_TERM ? render_all<DIMV, CH, 3, ES>(p, s) : render_all<DIMV, CH, 0, ES>(p, s)));
     switch (p.max_dim) {
         XW_CASE(7) XW_CASE(8) XW_CASE(11)
-        default: return indexed == 1 ? render_list<0, CH, ES>(p, s) : (indexed == 2 ? render_all<0, CH, 2, ES>(p, s) : (indexed == 3 ? render_all<0, CH, 3, ES>(p, s) : render_all<0, CH, 0, ES>(p, s)));
+        default: return m == RENDER_LIST ? render_list<0, CH, ES>(p, s) : (m == RENDER_ALIVE ? render_all<0, CH, 2, ES>(p, s) : (m == RENDER_ALL_TERM ? render_all<0, CH, 3, ES>(p, s) : render_all<0, CH, 0, ES>(p, s)));
     }
 #undef XW_CASE
 }
 
-hipError_t launch_xw_render(const XwParams &p, int indexed, hipStream_t s, hipEvent_t ev_front, hipEvent_t ev_list, hipEvent_t ev_cells) {
-    if (p.visible_radius) return launch_xw_render_ego(p, indexed == 3 ? 0 : indexed, s, ev_front, ev_list, ev_cells);
-    if (p.obs_f32) return p.channels == 3 ? render_dispatch<3, 4>(p, indexed, s) : render_dispatch<1, 4>(p, indexed, s);
-    return p.channels == 3 ? render_dispatch<3, 1>(p, indexed, s) : render_dispatch<1, 1>(p, indexed, s);
+hipError_t launch_xw_render(const XwParams &p, RenderMode m, hipStream_t s, hipEvent_t ev_front, hipEvent_t ev_list, hipEvent_t ev_cells) {
+    if (p.visible_radius) return launch_xw_render_ego(p, m == RENDER_ALL_TERM ? RENDER_ALL : m, s, ev_front, ev_list, ev_cells);
+    if (p.obs_f32) return p.channels == 3 ? render_dispatch<3, 4>(p, m, s) : render_dispatch<1, 4>(p, m, s);
+    return p.channels == 3 ? render_dispatch<3, 1>(p, m, s) : render_dispatch<1, 1>(p, m, s);
 }
 
 // The draw state of every env -- what a renderer elsewhere needs to reproduce the frames this batch shows (xwb_xw_pack_grids,
 // include/xwb.h "gather the state, not the pixels"): the cell codes each env's CURRENT frame was drawn from (icon + 1, target
 // bit stripped) and the context-ring operation of its last draw (xw_store_chunk's flag: 0 untouched, 1 ring shift, 2 fresh).
-// src = what the last frame-drawing verb read: 0 the live grid with fresh[]; 1 xwb_step's terminal snapshots (render mode 3);
-// 2 a list render (reset_done / reset_masked: the envs it drew are the ones at step 0).
+// src = what the last frame-drawing verb read (PACK_SRC_*).
 __global__ __launch_bounds__(256) void xw_pack_grids_kernel(XwParams p, int src, uint16_t *out_grid, uint8_t *out_flag) {
     const int cells = p.max_dim * p.max_dim;
     const size_t gi = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (gi >= (size_t)p.n * cells) return;
     const int e = (int)(gi / cells);
-    const bool term = src == 1 && p.term_flag[e];
+    const bool term = src == PACK_SRC_TERM && p.term_flag[e];
     out_grid[gi] = (term ? p.term_grid[gi] : p.grid[gi]) & CELL_ICON_MASK;
     if (out_flag && gi == (size_t)e * cells) {
         const bool at_start = p.num_steps[e] == 0;
-        out_flag[e] = (uint8_t)(src == 2 ? (at_start ? 2 : 0) : (term ? 1 : (at_start ? 2 : p.fresh[e])));
+        out_flag[e] = (uint8_t)(src == PACK_SRC_LIST ? (at_start ? 2 : 0) : (term ? 1 : (at_start ? 2 : p.fresh[e])));
     }
 }
 

@@ -579,7 +579,7 @@ __global__ __launch_bounds__(BS, 4) void xw_render_ego_kernel(XwParams p, const 
             }
         }
         EGO_T(6);
-        if (MODE == 1 && tid == 0 && p.list_flag == 2) { p.fresh[e] = 0; if (p.auto_reset == 2) p.done[e] = 0; }
+        if (MODE == 1 && tid == 0 && p.list_flag == 2) { p.fresh[e] = 0; if (p.auto_reset == AUTO_RESET_BY_LIST) p.done[e] = 0; }
     }
 }
 
@@ -910,7 +910,7 @@ template <int R, bool LIST>
 __global__ __launch_bounds__(64 * EgoCellsWaves<LIST>::NW) void xw_ego_cells_kernel(XwParams p, const uint8_t *map, int skip_term, const int32_t *count_now, int publish_step) {
     extern __shared__ uint4 smem4[];
     // (xwb_step_autoreset: this kernel running = the step kernel before it is complete; the reset's queue waits for that)
-    if (publish_step && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + 1, p.sig_epoch);
+    if (publish_step && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + SYNC_STEP, p.sig_epoch);
     ego_cells_body<R, LIST, false, EgoCellsWaves<LIST>::NW>(p, map, skip_term, count_now, (int)blockIdx.x, smem4);
 }
 
@@ -1062,7 +1062,7 @@ template <int CH, int R>
 __global__ __launch_bounds__(256) void xw_ego_eval_kernel(XwParams p, const uint32_t *atlas4, const uint16_t *layout, const uint8_t *map,
                                                           int publish, const EgoTap *comp) {
     // (this kernel running = the cells kernel queued before it is complete: xw_device.h, epochs instead of event packets)
-    if (publish && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + 5, p.sig_epoch);
+    if (publish && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + SYNC_SPAN_CELLS, p.sig_epoch);
     __shared__ EgoTap s_row[84][3], s_col[84][3];         // composed taps
     {   // (the host composed them: xw_ego_tables -- requested here, in front of everything else the body waits for)
         constexpr int O = R * (84 / R);
@@ -1449,7 +1449,7 @@ __device__ __forceinline__ void ego_gather_span(const XwParams &p, const EgoGath
 template <int CH, int R, bool CTX1, int ES, int PER>
 __global__ __launch_bounds__(EGO_BS) void xw_ego_gather_kernel(XwParams p, int skip_term, int publish) {
     typedef EgoSpanGeom<CH, R, ES, PER> G;
-    if (publish && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + 7, p.sig_epoch);      // the listed frames are out
+    if (publish && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + SYNC_SPAN_TERM, p.sig_epoch);      // the listed frames are out
     // (chunk indices fit 32 bits: the launcher checks)
     const unsigned n_chunks = (unsigned)p.n * G::cpf, c_lo = blockIdx.x * G::SPAN;
     const unsigned e0 = c_lo / G::cpf;
@@ -1467,7 +1467,7 @@ __global__ __launch_bounds__(EGO_BS) void xw_ego_gather_kernel(XwParams p, int s
 template <int CH, int R, bool CTX1, int ES>
 __global__ __launch_bounds__(EGO_BS) void xw_ego_gather_list_kernel(XwParams p, const int32_t *count_now, int publish) {
     typedef EgoSpanGeom<CH, R, ES, 2> G;
-    if (publish && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + 6, p.sig_epoch);      // the evaluation kernel is through
+    if (publish && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + SYNC_SPAN_EVAL, p.sig_epoch);      // the evaluation kernel is through
     const int cnt = *count_now, part = blockIdx.x % G::SPE;
     EGO_GATHER_LDS(G, R, lds);
     for (int item = blockIdx.x / G::SPE; item < cnt; item += gridDim.x / G::SPE) {
@@ -1476,7 +1476,7 @@ __global__ __launch_bounds__(EGO_BS) void xw_ego_gather_list_kernel(XwParams p, 
         ego_gather_span<CH, R, CTX1, ES, 2>(p, lds, (unsigned)e, (unsigned)cr, G::cpf - cr < G::SPAN ? G::cpf - cr : G::SPAN, 0, p.list_flag);
         // (as the list render of the other path: the first frame of a new episode consumes fresh[] and, where the reset left
         // that to the render, the done code)
-        if (part == 0 && threadIdx.x == 0 && p.list_flag == 2) { p.fresh[e] = 0; if (p.auto_reset == 2) p.done[e] = 0; }
+        if (part == 0 && threadIdx.x == 0 && p.list_flag == 2) { p.fresh[e] = 0; if (p.auto_reset == AUTO_RESET_BY_LIST) p.done[e] = 0; }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *p.ego_miss_count = 0;          // (the list this path's cells kernel filled is consumed)
 }
@@ -1767,8 +1767,8 @@ hipError_t launch_xw_ego_build_tab(const XwParams &p, hipStream_t s) {
 namespace {
 template <int CH, int R>
 hipError_t ego_span_render_list(const XwParams &p0, const EgoTables &t, hipStream_t s, int parts);
-// mode 0: every env; 2: every env the last step did not finish (a reset runs beside this: their state is in flux);
-// 4: a step's frames -- every env, the finished ones first and from the list (p.list_flag says how their context moves),
+// mode 0 (RENDER_ALL): every env; 2 (RENDER_ALIVE): every env the last step did not finish (a reset runs beside this: their
+// state is in flux); 4 (RENDER_SPAN_STEP): a step's frames -- every env, the finished ones first and from the list (p.list_flag says how their context moves),
 //    ev_cells recorded once nothing reads the grids and agents any more (a reset's map generator may start), ev_front once
 //    nothing reads the goal images either (they may be redrawn), ev_list once the listed frames are out
 template <int CH, int R>
@@ -1871,7 +1871,7 @@ hipError_t ego_span_render_list(const XwParams &p0, const EgoTables &t, hipStrea
     const size_t cells_lds = EPW * cells * 3 + ((p.n_icons + 15) & ~15) + ((p.n_icons + 2 + 15) & ~15);
     const int n_cap = p.n < 16384 ? p.n : 16384;               // (workgroups beyond the list leave at once)
     if (parts & 1) {
-        // (parts & 4: the goal images of these envs are still to be redrawn -- launch_xw_reset with defer_warp -- in the same launch)
+        // (parts & 4: the goal images of these envs are still to be redrawn -- the reset left them to this launch)
         const int nb_cells = (p.n + EPW - 1) / EPW;
         if (parts & 4) hipLaunchKernelGGL((xw_ego_list_front_kernel<R>), dim3(nb_cells + 4096), dim3(256), cells_lds, s, p, t.map, a4, cnt, nb_cells);
         else hipLaunchKernelGGL((xw_ego_cells_kernel<R, true>), dim3(nb_cells), dim3(256), cells_lds, s, p, t.map, 0, cnt, 0);
@@ -1888,23 +1888,34 @@ hipError_t ego_span_render_list(const XwParams &p0, const EgoTables &t, hipStrea
 }
 }  // namespace
 
-hipError_t launch_xw_render_ego(const XwParams &p, int indexed, hipStream_t s, hipEvent_t ev_front, hipEvent_t ev_list, hipEvent_t ev_cells) {
+// the parts of the span path's list render a mode draws (ego_span_render_list's `parts`), 0: not a list render
+static int span_list_parts(RenderMode m) {
+    switch (m) {
+        case RENDER_LIST: return 3;
+        case RENDER_LIST_FRONT: return 1;
+        case RENDER_LIST_GATHER: return 2;
+        case RENDER_LIST_FRONT_WARP: return 5;
+        case RENDER_LIST_WARP: return 7;
+        default: return 0;
+    }
+}
+
+hipError_t launch_xw_render_ego(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front, hipEvent_t ev_list, hipEvent_t ev_cells) {
     const EgoTables t = ego_tables_of(p);
     const int r = p.visible_radius, O = p.out_dim, O4 = (O + 3) & ~3, D = p.max_dim;
     const int CH = p.channels;
-    if (indexed != 1 && indexed < 5 && xw_ego_span(p)) {
-        const int m = indexed;
+    const int parts = span_list_parts(mode);
+    if (!parts && mode <= RENDER_SPAN_STEP && xw_ego_span(p)) {
+        const int m = mode;                                    // (ego_span_render's mode: RENDER_ALL, RENDER_ALIVE or RENDER_SPAN_STEP)
         if (CH == 3) return r == 3 ? ego_span_render<3, 3>(p, t, m, s, ev_front, ev_list, ev_cells) : (r == 5 ? ego_span_render<3, 5>(p, t, m, s, ev_front, ev_list, ev_cells) : ego_span_render<3, 7>(p, t, m, s, ev_front, ev_list, ev_cells));
         return r == 3 ? ego_span_render<1, 3>(p, t, m, s, ev_front, ev_list, ev_cells) : (r == 5 ? ego_span_render<1, 5>(p, t, m, s, ev_front, ev_list, ev_cells) : ego_span_render<1, 7>(p, t, m, s, ev_front, ev_list, ev_cells));
     }
-    // (5 / 6: the front kernels / the gather of the list render alone -- xwb_reset_done runs them on two queues; 7: as 5, with
-    // the goal images of the listed envs redrawn in the same launch as their cell tables; 8: as 1, with that launch)
-    if ((indexed == 1 || (indexed >= 5 && indexed <= 8)) && xw_ego_span(p) && p.ego_cellsrc_list) {
-        const int parts = indexed == 5 ? 1 : (indexed == 6 ? 2 : (indexed == 7 ? 5 : (indexed == 8 ? 7 : 3)));
+    // (the parts alone: xwb_reset_done runs them on two queues)
+    if (parts && xw_ego_span(p) && p.ego_cellsrc_list) {
         if (CH == 3) return r == 3 ? ego_span_render_list<3, 3>(p, t, s, parts) : (r == 5 ? ego_span_render_list<3, 5>(p, t, s, parts) : ego_span_render_list<3, 7>(p, t, s, parts));
         return r == 3 ? ego_span_render_list<1, 3>(p, t, s, parts) : (r == 5 ? ego_span_render_list<1, 5>(p, t, s, parts) : ego_span_render_list<1, 7>(p, t, s, parts));
     }
-    if (indexed >= 4) return hipErrorInvalidValue;             // (only the span path draws a step's terminal frames itself)
+    if (mode >= RENDER_SPAN_STEP) return hipErrorInvalidValue;   // (only the span path draws a step's terminal frames itself)
     const bool fast = p.ego_fast != 0;
     const size_t lds = ego_frame_bytes(p) + (size_t)r * r * sizeof(EgoCell) + (fast ? (size_t)ego_layout_words(O4, r) * 8 : 0) +
                        (size_t)p.n_icons * 4 + (size_t)((p.n_icons + 3) & ~3) + (size_t)((D * D + 3) & ~3) +
@@ -1912,12 +1923,13 @@ hipError_t launch_xw_render_ego(const XwParams &p, int indexed, hipStream_t s, h
     // whole batch: looping workgroups, each with its next env's state in flight, so the per-workgroup prologue (taps and
     // layout tables -> LDS) is amortised; 8192 of them rather than the 1024 that are resident at once: a shorter tail, and
     // a reset_done running on the side stream finds free slots (MI355X, C4 batch: 0.518 ms per step with 1024, 0.494 with 8192)
-    const unsigned blocks = indexed == 1 ? 2048u : (unsigned)(p.n < 8192 ? p.n : 8192);
+    const bool list = mode == RENDER_LIST;
+    const unsigned blocks = list ? 2048u : (unsigned)(p.n < 8192 ? p.n : 8192);
     const int32_t *cnt = (const int32_t *)p.done_count;
     const uint32_t *a4 = reinterpret_cast<const uint32_t *>(p.atlas64);
 #define EGO_LAUNCH2(CHV, MODEV, BSV, FASTV) hipLaunchKernelGGL((xw_render_ego_kernel<CHV, MODEV, BSV, FASTV>), dim3(blocks), dim3(BSV), lds, s, p, a4, t.h1, t.v1, t.h2, t.v2, t.lut, p.ego_tab, cnt)
 #define EGO_LAUNCH1(CHV, MODEV, BSV) do { if (fast) EGO_LAUNCH2(CHV, MODEV, BSV, true); else EGO_LAUNCH2(CHV, MODEV, BSV, false); } while (0)
-#define EGO_LAUNCH(CHV) do { if (indexed == 1) { if (p.ego_list_beside) EGO_LAUNCH1(CHV, 1, 256); else EGO_LAUNCH1(CHV, 1, 1024); } else if (indexed == 2) EGO_LAUNCH1(CHV, 2, 256); else EGO_LAUNCH1(CHV, 0, 256); } while (0)
+#define EGO_LAUNCH(CHV) do { if (list) { if (p.ego_list_beside) EGO_LAUNCH1(CHV, 1, 256); else EGO_LAUNCH1(CHV, 1, 1024); } else if (mode == RENDER_ALIVE) EGO_LAUNCH1(CHV, 2, 256); else EGO_LAUNCH1(CHV, 0, 256); } while (0)
     if (CH == 3) EGO_LAUNCH(3); else EGO_LAUNCH(1);
 #undef EGO_LAUNCH
 #undef EGO_LAUNCH1

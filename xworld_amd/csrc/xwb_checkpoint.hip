@@ -11,7 +11,8 @@ extern "C++" {
 namespace {
 struct StateArray { void *ptr; size_t bytes; };
 
-std::vector<StateArray> state_arrays(xwb_sim *s, bool include_obs) {
+// list_sel / count_sel: which buffers of the done list's and its counter's rotation are the state's
+std::vector<StateArray> state_arrays(xwb_sim *s, bool include_obs, int list_sel, int count_sel) {
     const size_t n = (size_t)s->n;
     std::vector<StateArray> a;
     auto add = [&](void *p, size_t bytes) { if (p) a.push_back(StateArray{p, bytes}); };
@@ -25,7 +26,7 @@ std::vector<StateArray> state_arrays(xwb_sim *s, bool include_obs) {
         add(s->d_grid, n * cells * 2); add(s->d_agent, n * 4); add(s->d_task_steps, n * 4); add(s->d_task_state, n * 4);
         add(s->d_task_steps2, n * 4); add(s->d_task_state2, n * 4); add(s->d_grp_order, n);
         // (the done list and its counter rotate through two / three buffers: the current ones are saved, a load rewinds the rotation)
-        add(s->d_done_list + (size_t)s->list_sel * n, n * 4); add(s->d_done_count + s->count_sel, 4); add(s->d_fresh, n); add(s->d_perf, 40 * 8);
+        add(s->d_done_list + (size_t)list_sel * n, n * 4); add(s->d_done_count + count_sel, 4); add(s->d_fresh, n); add(s->d_perf, 40 * 8);
         add(s->d_goal_cells, n * XW_MAX_GOALS); add(s->d_cand2d, n * 4); add(s->d_agent_dir, n); add(s->d_sent_names, n * 4);
         add(s->d_goal_warp, n * XW_MAX_GOALS * 6 * sizeof(double));     // goal images are re-warped from these on load
         add(s->d_cur_level, n); add(s->d_cur_counter, n * 4); add(s->d_cur_usage, n * 9 * XW_USAGE_BYTES);
@@ -64,7 +65,7 @@ uint64_t config_hash(const xwb_config &c) {            // everything that shapes
 int xwb_state_bytes(xwb_sim *s, int32_t include_obs, size_t *bytes) {
     if (!s || !bytes) return fail(XWB_ERR_ARG, "NULL argument");
     size_t total = sizeof(StateHeader);
-    for (auto &a : state_arrays(s, include_obs != 0)) total += 8 + a.bytes;
+    for (auto &a : state_arrays(s, include_obs != 0, s->list_sel, s->count_sel)) total += 8 + a.bytes;
     *bytes = total;
     return XWB_OK;
 }
@@ -77,7 +78,7 @@ int xwb_save_state(xwb_sim *s, int32_t include_obs, uint8_t *out_host, size_t ca
     xwb_state_bytes(s, include_obs, &need);
     if (cap < need) return fail(XWB_ERR_ARG, "buffer smaller than xwb_state_bytes");
     HIP_TRY(hipDeviceSynchronize());
-    const auto arrays = state_arrays(s, include_obs != 0);
+    const auto arrays = state_arrays(s, include_obs != 0, s->list_sel, s->count_sel);
     StateHeader h{};
     memcpy(h.magic, "XWBSTATE", 8);
     h.version = XWB_STATE_VERSION; h.game = (uint32_t)s->cfg.game; h.num_envs = (uint32_t)s->n; h.include_obs = include_obs ? 1u : 0u;
@@ -108,29 +109,35 @@ int xwb_load_state(xwb_sim *s, const uint8_t *in_host, size_t bytes) {
     if (h.game != (uint32_t)s->cfg.game || h.num_envs != (uint32_t)s->n || h.obs_bytes_per_env != s->obs_bytes_per_env ||
         h.cfg_hash != config_hash(s->cfg))
         return fail(XWB_ERR_ARG, "state blob was saved from a batch with another configuration");
-    HIP_TRY(hipDeviceSynchronize());
-    s->count_sel = 0; s->list_sel = 0;                  // the saved list and counter become the rotation's current ones
-    const auto arrays = state_arrays(s, h.include_obs != 0);
+    // the whole blob is checked before anything changes: a refused load leaves the batch as it was.  The saved list and counter
+    // become the first buffers of the rotation.
+    const auto arrays = state_arrays(s, h.include_obs != 0, 0, 0);
     if (arrays.size() != h.n_arrays) return fail(XWB_ERR_ARG, "state blob layout mismatch");
-    if (s->d_done_count) HIP_TRY(hipMemset(s->d_done_count, 0, 3 * sizeof(int32_t)));
-    const uint8_t *r = in_host + sizeof h, *end = in_host + bytes;
+    size_t at = sizeof h;
     for (auto &a : arrays) {
         uint64_t b;
-        if (r + 8 > end) return fail(XWB_ERR_ARG, "truncated state blob");
-        memcpy(&b, r, 8); r += 8;
-        if (b != a.bytes || r + b > end) return fail(XWB_ERR_ARG, "state blob layout mismatch");
-        HIP_TRY(hipMemcpy(a.ptr, r, a.bytes, hipMemcpyHostToDevice));
-        r += b;
+        if (bytes - at < 8) return fail(XWB_ERR_ARG, "truncated state blob");
+        memcpy(&b, in_host + at, 8); at += 8;
+        if (b != a.bytes || b > bytes - at) return fail(XWB_ERR_ARG, "state blob layout mismatch");
+        at += b;
     }
-    s->shadow_ok = false; s->regen_pending = false; s->step_lazy = false; s->regen_deferred = false; s->snap_ok = false; s->step_fused = false;
-    s->frame_src = 0; s->draws_since_pack = 0;
+    HIP_TRY(hipDeviceSynchronize());
+    step_record_invalidate(s);
+    s->count_sel = 0; s->list_sel = 0;
+    if (s->d_done_count) HIP_TRY(hipMemset(s->d_done_count, 0, 3 * sizeof(int32_t)));
+    at = sizeof h;
+    for (auto &a : arrays) {
+        HIP_TRY(hipMemcpy(a.ptr, in_host + at + 8, a.bytes, hipMemcpyHostToDevice));
+        at += 8 + a.bytes;
+    }
+    s->frame_src = PACK_SRC_LIVE; s->draws_since_pack = 0;
     s->policy_step = h.policy_step; s->list_valid = (h.list_valid & 1u) != 0; s->autoreset_done = (h.list_valid & 2u) != 0;
     if (s->cfg.game == XWB_XWORLD2D) {
         XwParams p = xw_params(s);
         if (p.visible_radius) HIP_TRY(launch_xw_warp_goals(p, false, nullptr));
         if (!h.include_obs) {                           // frames from the state; older context frames start black
             HIP_TRY(hipMemset(s->d_fresh, 2, (size_t)s->n));
-            HIP_TRY(launch_xw_render(p, 0, nullptr));
+            HIP_TRY(launch_xw_render(p, RENDER_ALL, nullptr));
         }
     }
     HIP_TRY(hipDeviceSynchronize());

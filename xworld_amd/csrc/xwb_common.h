@@ -88,6 +88,49 @@ enum : int { ACTION_SKIP = -1 };
 // which envs a state-changing kernel applies to
 enum : int { MODE_STEP = 0, MODE_RESET_ALL = 1, MODE_RESET_DONE = 2, MODE_RESET_MASK = 3 };
 
+// The words of XwParams::sync: epochs one queue of the step loop publishes and the other waits for (xw_device.h
+// xw_publish_epoch / xw_wait_epoch), the probe's own words and the poison word.  A publisher is the first thread of the kernel
+// that FOLLOWS the producer in its queue, or a one-thread signal kernel queued behind it.
+enum SyncSlot : int {
+    SYNC_PROBE = 0,              // the concurrency probe's token (xwb_verbs.hip epoch_probe)
+    SYNC_STEP = 1,               // the step kernel is complete
+    SYNC_PROBE_EXPIRED = 2,      // the probe's waiter gave up (the probe's flag, not the batch's poison word)
+    SYNC_RESET = 3,              // the reset kernel (and the side queue's work queued behind it) is complete
+    SYNC_POISON = 4,             // != 0: a wait's watchdog expired, the batch is poisoned
+    SYNC_SPAN_CELLS = 5,         // egocentric span path: the step's cells kernel, the last reader of the grids, is through
+    SYNC_SPAN_EVAL = 6,          // ... its evaluation kernel, the last reader of the goal images
+    SYNC_SPAN_TERM = 7,          // ... its list gather: the terminal frames are out
+    SYNC_REGEN = 8,              // the last regeneration pass of pre-generated episodes is complete
+};
+
+// XwParams::auto_reset: who clears the done codes of the envs a reset starts
+enum : int {
+    AUTO_RESET_CLEAR = 0,        // the reset kernel
+    AUTO_RESET_KEEP = 1,         // nobody: they stay for the caller to read (xwb_step_autoreset)
+    AUTO_RESET_BY_LIST = 2,      // the list render: the reset runs beside work on the caller's queue that may still read them
+};
+
+// xw_pack_grids_kernel's src: what the last frame-drawing verb read
+enum : int {
+    PACK_SRC_LIVE = 0,           // the live grid, with fresh[]
+    PACK_SRC_TERM = 1,           // xwb_step's terminal snapshots (RENDER_ALL_TERM)
+    PACK_SRC_LIST = 2,           // a list render: the envs it drew are the ones at step 0
+};
+
+// what launch_xw_render / launch_xw_render_ego draw
+enum RenderMode : int {
+    RENDER_ALL = 0,              // every env
+    RENDER_LIST = 1,             // the envs of the compacted done list
+    RENDER_ALIVE = 2,            // every env whose done code is 0 (the rest follows as a list)
+    RENDER_ALL_TERM = 3,         // every env, those the step just finished from their terminal snapshot (term_grid)
+    RENDER_SPAN_STEP = 4,        // egocentric span path: a step's frames (kernels_xworld_ego.hip ego_span_render)
+    // the span path's list render in parts (ego_span_render_list):
+    RENDER_LIST_FRONT = 5,       // its two front kernels
+    RENDER_LIST_GATHER = 6,      // its gather
+    RENDER_LIST_FRONT_WARP = 7,  // as RENDER_LIST_FRONT, the listed envs' goal images redrawn in the first launch
+    RENDER_LIST_WARP = 8,        // the whole list render, with that first launch
+};
+
 // ------------------------------------------------------------ SimpleGame ---
 struct SgParams {
     int n, array_size, context, max_steps, act_rep, mode, auto_reset, n_steps;
@@ -277,7 +320,7 @@ struct XwParams {
     //                  rewrites beside it) -- 3 us off the step kernel, 2 off the render on C4.
     // Regeneration runs on the side queue beside the render, two slots per env so that it never writes what an installer may
     // still read; whoever touches the done list next (the step kernel's wavefronts that hold a finished env, the thread that
-    // zeroes the rotating counter, the installing list render) first waits, device-side, for it: sync[8] >= regen_wait.
+    // zeroes the rotating counter, the installing list render) first waits, device-side, for it: sync[SYNC_REGEN] >= regen_wait.
     int shadow, swap_shadow, list_swap;
     uint32_t regen_wait;
     uint32_t *sh_ep;
@@ -298,14 +341,14 @@ struct XwParams {
     uint16_t *snap_grid_out;
     int snap_act_rep;            // act_rep of the predicted move (the list render's; the step kernel predicts with its own)
     // device-side hand-off between the two queues of the step loop, instead of event / barrier packets (each costs the
-    // loop ~3-6 us of idle GPU): sync[1] = epoch of the last completed step kernel, sync[3] = of the last completed reset
-    // kernel, sync[4] != 0: a wait gave up (xw_device.h: xw_publish_epoch / xw_wait_epoch).  render_all with sig_epoch != 0 publishes it to sync[1] when it
-    // starts (= the step kernel before it in the queue is complete); the list render with wait_epoch != 0 waits for sync[3].
+    // loop ~3-6 us of idle GPU): the words are named by SyncSlot.  render_all with sig_epoch != 0 publishes it to
+    // sync[SYNC_STEP] when it starts (= the step kernel before it in the queue is complete); the list render with
+    // wait_epoch != 0 waits for sync[wait_slot].
     uint32_t *sync;
-    uint32_t *poison_host;       // pinned host word raised together with sync[4] when a wait's watchdog expires (the host reads
-                                 // it at the top of every verb without a sync: the batch is poisoned from then on)
+    uint32_t *poison_host;       // pinned host word raised together with sync[SYNC_POISON] when a wait's watchdog expires (the
+                                 // host reads it at the top of every verb without a sync: the batch is poisoned from then on)
     uint32_t sig_epoch, wait_epoch;
-    int wait_slot;               // the list render's wait: sync[wait_slot] >= wait_epoch (3: the reset kernel's epoch, 8: the regeneration's)
+    int wait_slot;               // the list render's wait: a SyncSlot (SYNC_RESET: the reset kernel's epoch, SYNC_REGEN: the regeneration's)
     uint32_t *minstd;            // nullable: XWB_RNG_MINSTD, one libstdc++ minstd_rand0 state per env: the teacher's task draw
     int dbg_ego_per, dbg_ego_pad, dbg_render_shape;   // xwb_config.debug_* (launch-shape A/B switches; 0 = defaults)
     int dbg_ego_miss_blocks;     // XWB_DEBUG ego_miss_blocks=N: goal-cell workgroups of the whole-batch evaluation launch (0 = the default)
@@ -324,24 +367,18 @@ hipError_t launch_xw_wait(const uint32_t *epoch_slot, uint32_t want, uint32_t *p
                           unsigned long long budget_ticks = 0);
 // one thread that publishes `value`: queued behind a kernel, it tells the other queue that kernel is complete
 hipError_t launch_xw_signal(uint32_t *epoch_slot, uint32_t value, hipStream_t s);
-// reset envs: mode RESET_ALL -> every env; otherwise the compacted done_list / done_count
-// before_warp (egocentric): the redraw of the goal images waits for it (kernels still reading the old images);
-// defer_warp: the goal images are left to the caller (launch_xw_render(p, 7, ...): redrawn beside the list's cell tables)
-hipError_t launch_xw_reset(const XwParams &p, int mode, hipStream_t s, hipEvent_t before_warp = nullptr, const uint32_t *warp_epoch_slot = nullptr,
-                           uint32_t warp_epoch = 0, int defer_warp = 0);
+// reset envs: mode RESET_ALL -> every env; otherwise the compacted done_list / done_count.  Egocentric: the goal images of
+// the reset envs are the caller's to redraw (launch_xw_warp_goals, or a list render's RENDER_*_WARP)
+hipError_t launch_xw_reset(const XwParams &p, int mode, hipStream_t s);
 // compaction of done[] (mode RESET_DONE) or mask (RESET_MASK) into done_list / done_count
 hipError_t launch_xw_compact(const XwParams &p, int mode, hipStream_t s);
-// the batch's draw state (cell codes its current frames show + context-ring flags) for a renderer elsewhere; src: see the kernel
+// the batch's draw state (cell codes its current frames show + context-ring flags) for a renderer elsewhere; src: PACK_SRC_*
 hipError_t launch_xw_pack_grids(const XwParams &p, int src, uint16_t *out_grid, uint8_t *out_flag, hipStream_t s);
-// render: indexed == 0 -> all envs (LDS-resident atlas, persistent workgroups);
-//         indexed == 1 -> envs in done_list (atlas through L2)
-// indexed: 0 = every env, 1 = the compacted done list, 2 = every env whose done code is 0 (the rest follows as a list),
-// 3 = every env, those the step just finished from their terminal snapshot (term_grid)
-hipError_t launch_xw_render(const XwParams &p, int indexed, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);
-// egocentric: indexed 4 = a step's frames on the span path (kernels_xworld_ego.hip), see ego_span_render; the list render of the
-// span path in parts (ego_span_render_list): 5 = its two front kernels, 6 = its gather, 7 = as 5 with the listed envs' goal images
-// redrawn in the first launch (launch_xw_reset's defer_warp), 8 = everything, with that first launch
-hipError_t launch_xw_render_ego(const XwParams &p, int indexed, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);
+// full observation: RENDER_ALL / RENDER_ALIVE / RENDER_ALL_TERM (LDS-resident atlas, persistent workgroups), RENDER_LIST (atlas
+// through L2); egocentric: launch_xw_render_ego (RENDER_ALL_TERM draws as RENDER_ALL there)
+hipError_t launch_xw_render(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);
+// RENDER_SPAN_STEP and RENDER_LIST_* need the span path; the events are RENDER_SPAN_STEP's (kernels_xworld_ego.hip ego_span_render)
+hipError_t launch_xw_render_ego(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);
 bool xw_ego_span(const XwParams &p);
 hipError_t launch_xw_warp_goals(const XwParams &p, bool list, hipStream_t s);
 struct EgoTap;

@@ -390,7 +390,7 @@ int xw_setup(xwb_sim *s) {
     for (int i = 0; i < 8; ++i) p.task_acc2[i] = (i ? p.task_acc2[i - 1] : 0.0) + (i < c.n_tasks2 && p.task_weighted2 ? c.task_weights2[i] : 0.0);
     p.task_state2 = s->d_task_state2; p.task_steps2 = s->d_task_steps2;
     p.perf = s->d_perf;
-    p.shadow = 0; p.swap_shadow = 0; p.list_swap = 0; p.regen_wait = 0; p.wait_slot = 3; p.sh_ep = s->d_sh_ep;
+    p.shadow = 0; p.swap_shadow = 0; p.list_swap = 0; p.regen_wait = 0; p.wait_slot = SYNC_RESET; p.sh_ep = s->d_sh_ep;
     p.sh_grid = s->d_sh_grid; p.sh_agent_xy = s->d_sh_agent; p.sh_task_state = s->d_sh_task_state; p.sh_task_state2 = s->d_sh_task_state2;
     p.sh_sent_names = s->d_sh_sent_names; p.sh_cand2d = s->d_sh_cand2d; p.sh_goal_cells = s->d_sh_goal_cells;
     p.exclusive = exclusive ? 1 : 0;

@@ -66,6 +66,15 @@ struct xwb_sim {
     int num_actions = 0;
     uint32_t policy_step = 0;
     bool list_valid = false;
+    // what the last step call leaves for the verbs after it (xwb_verbs.hip): set by every xworld step call, cleared by
+    // step_record_invalidate when the state it describes is replaced
+    struct StepRecord {
+        int path = XWB_PATH_NONE;          // the kernel sequence it ran; XWB_PATH_NONE: nothing of it is pending any more
+        bool epochs = false;               // its hand-overs are epochs: a later verb's waiters wait for what its kernels publish
+                                           // (kept by step_record_invalidate: xwb_step_path reports it)
+        bool step_pub_queued = false;      // a kernel that publishes its epoch to sync[SYNC_STEP] is in the caller's queue (after a
+                                           // fused launch that is xwb_reset_done's list render: until then, waiters use events)
+    } rec;
     // xwb_xw_pack_grids: what the last frame-drawing verb read (xw_pack_grids_kernel's src) and how many such verbs ran since
     // the last pack (a context ring can only be replayed elsewhere one draw at a time)
     int frame_src = 0, draws_since_pack = 0;
@@ -78,7 +87,7 @@ struct xwb_sim {
     uint64_t step_seq = 0;                 // xworld step calls so far
     bool profiling = false;
     xwb::host::KernelTimer t_render, t_step, t_reset, t_list;   // t_list: the list render (first frames of the envs a reset started)
-    int last_path = XWB_PATH_NONE;           // xwb_step_path: which kernel sequence the last step call ran
+    int last_path = XWB_PATH_NONE;         // xwb_step_path: which kernel sequence the last step call ran
     hipStream_t side = nullptr;            // reset of finished envs runs here, beside render_all
     uint32_t *d_minstd = nullptr;          // XWB_RNG_MINSTD: one engine state per env
     uint32_t *d_sync = nullptr;            // device-side epochs of the step / reset kernels (XwParams::sync)
@@ -87,16 +96,11 @@ struct xwb_sim {
     struct StreamProbe { hipStream_t st; bool ok; int reason; };
     std::vector<StreamProbe> probes;
     int sync_reason = XWB_SYNC_REASON_NOT_USED;
-    bool step_epochs = false;              // the last step call's hand-overs were epochs (a following reset_done follows suit:
-                                           // its waiters wait for what that step's kernels publish)
     uint32_t probe_token = 0;
     uint32_t *h_poison = nullptr;          // pinned host word: a watchdog expired (XwParams::poison_host points at it)
     bool poisoned = false;
     hipEvent_t ev_step = nullptr, ev_reset = nullptr, ev_term = nullptr, ev_cells = nullptr;
     hipEvent_t ev_results = nullptr;       // xwb_gather_results_beside's hand-over when the last step did not run on epochs (made on first use)
-    bool results_by_epoch = false;         // the last step call published "step kernel complete" as an epoch in sync[1]
-    bool span_epochs = false;              // ... and handed over through epochs (d_sync[5..7]) rather than those events
-    bool span_step = false;                // the last step drew its frames on the egocentric span path (ev_cells / ev_step / ev_term are its)
     // common device buffers
     int32_t *d_actions_in = nullptr;       // staging for xwb_step_host
     uint8_t *d_mask = nullptr;             // staging for xwb_reset_env
@@ -121,8 +125,7 @@ struct xwb_sim {
     unsigned long long *d_perf = nullptr;  // XwParams::perf
     // pre-generated next episodes (XwParams::shadow / swap_shadow): xwb_step_autoreset's fast path
     bool pregen = false, shadow_ok = false, regen_pending = false, regen_by_epoch = false;
-    bool regen_deferred = false, regen_deferred_by_epoch = false;   // xwb_reset_done after a fused step: the pass is queued by the next verb
-    bool step_lazy = false;                // the last plain step kept no terminal snapshot: its reset_done installs shadows
+    bool regen_deferred = false;           // xwb_reset_done after a fused step: the pass is queued by the next verb (in the step's mode)
     int shadow_breaks = 0;                 // times another verb made the shadows stale (the lazy default path gives up after a few)
     uint32_t epoch_regen = 0, epoch_regen_prev = 0;   // epochs of the last two regeneration passes handed over by epoch ...
     uint64_t regen_seq = 0, regen_seq_prev = 0;       // ... and the step calls (step_seq) whose lists they read
@@ -131,9 +134,7 @@ struct xwb_sim {
     // snapshot clears snap_ok, and the next xwb_step then runs step -> render as two launches again
     uint16_t *d_snap_grid[2] = {nullptr, nullptr};
     int snap_sel = 0, snap_act_rep = 1;
-    bool snap_ok = false, step_fused = false;
-    bool step_pub_queued = false;          // a kernel that publishes the last step call's epoch is in the caller's queue (after a fused
-                                           // launch that is xwb_reset_done's list render: until then, results are handed over by an event)
+    bool snap_ok = false;
     uint32_t snap_step = 0;
     uint32_t *d_sh_ep = nullptr, *d_done_ep = nullptr;
     uint8_t *d_sh_goal_cells = nullptr;
@@ -207,6 +208,7 @@ inline bool is_poisoned(xwb_sim *s) {
     if (!s->poisoned && s->h_poison && *(volatile uint32_t *)s->h_poison) s->poisoned = true;
     return s->poisoned;
 }
+#define XWB_TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)   // (a host helper's XWB_* code)
 #define XWB_LIVE(s) do { if (::xwb::host::is_poisoned(s)) return ::xwb::host::fail(XWB_ERR_STATE, ::xwb::host::POISON_MSG); } while (0)
 
 // ---- xwb_verbs.hip ----
@@ -218,6 +220,8 @@ bool epoch_probe(xwb_sim *s, hipStream_t st, int *reason);
 bool side_beside(xwb_sim *s, hipStream_t st, int *reason);
 // -1: the environment / a tool does not override the hand-over mode, 0: events, 1: epochs
 int queue_sync_env(int *reason);
+// what a step call leaves behind is void (the live state was replaced): nothing of it is pending any more
+void step_record_invalidate(xwb_sim *s);
 void timer_begin(xwb_sim *s, KernelTimer &t, hipStream_t st);
 void timer_end(xwb_sim *s, KernelTimer &t, hipStream_t st);
 SgParams sg_params(xwb_sim *s);
@@ -226,7 +230,6 @@ XwParams xw_params(xwb_sim *s);
 int join_regen(xwb_sim *s, hipStream_t st);
 int launch_regen(xwb_sim *s, bool by_epoch);
 int flush_regen(xwb_sim *s);
-int xw_reset_list(xwb_sim *s, int mode, bool keep_done, bool render, hipStream_t st, bool beside_render = false);
 
 // ---- xwb_sentence_ids.hip ----
 // compiles the word-id tables from the vocabulary and the names and uploads them (synchronises the device); both must be set

@@ -31,28 +31,34 @@ int queue_sync_env(int *reason) {
     return mode;
 }
 
+// the next epoch of a counter (0 means "nothing to wait for")
+uint32_t next_epoch(uint32_t &e) {
+    if (++e == 0) e = 1;
+    return e;
+}
+
 // One-time probe of (caller stream, s->side): do kernels of the two really run concurrently?  A waiter with a 2 ms watchdog
 // is enqueued FIRST on one stream, its publisher on the other, in both directions; on streams that share a hardware queue
-// (or under a tool that serialises kernels) the waiter runs alone, expires and raises the probe's own flag (d_sync[2], not
-// the batch's poison word).  Both streams are drained before and after, so work of the caller that is still queued cannot
+// (or under a tool that serialises kernels) the waiter runs alone, expires and raises the probe's own flag
+// (sync[SYNC_PROBE_EXPIRED], not the batch's poison word).  Both streams are drained before and after, so work of the caller that is still queued cannot
 // make the probe fail (or be delayed by it) -- the cost is one synchronisation the first time a stream is seen.
 bool epoch_probe(xwb_sim *s, hipStream_t st, int *reason) {
     auto bad = [&](int why) { (void)hipGetLastError(); *reason = why; return false; };
     if (hipStreamSynchronize(st) != hipSuccess || hipStreamSynchronize(s->side) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
-    if (hipMemsetAsync(s->d_sync + 2, 0, sizeof(uint32_t), s->side) != hipSuccess || hipStreamSynchronize(s->side) != hipSuccess)
+    if (hipMemsetAsync(s->d_sync + SYNC_PROBE_EXPIRED, 0, sizeof(uint32_t), s->side) != hipSuccess || hipStreamSynchronize(s->side) != hipSuccess)
         return bad(XWB_SYNC_REASON_PROBE_ERROR);
     for (int dir = 0; dir < 2; ++dir) {
         hipStream_t waiter = dir ? st : s->side, publisher = dir ? s->side : st;
-        if (++s->probe_token == 0) s->probe_token = 1;
-        if (launch_xw_wait(s->d_sync + 0, s->probe_token, s->d_sync + 2, nullptr, waiter, 200000ull) != hipSuccess)   // 2 ms
+        next_epoch(s->probe_token);
+        if (launch_xw_wait(s->d_sync + SYNC_PROBE, s->probe_token, s->d_sync + SYNC_PROBE_EXPIRED, nullptr, waiter, 200000ull) != hipSuccess)   // 2 ms
             return bad(XWB_SYNC_REASON_PROBE_ERROR);
-        if (launch_xw_signal(s->d_sync + 0, s->probe_token, publisher) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
+        if (launch_xw_signal(s->d_sync + SYNC_PROBE, s->probe_token, publisher) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
         if (hipStreamSynchronize(waiter) != hipSuccess || hipStreamSynchronize(publisher) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
     }
     uint32_t expired = 1;
-    if (hipMemcpy(&expired, s->d_sync + 2, sizeof expired, hipMemcpyDeviceToHost) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
+    if (hipMemcpy(&expired, s->d_sync + SYNC_PROBE_EXPIRED, sizeof expired, hipMemcpyDeviceToHost) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
     if (expired) {
-        (void)hipMemset(s->d_sync + 2, 0, sizeof(uint32_t));
+        (void)hipMemset(s->d_sync + SYNC_PROBE_EXPIRED, 0, sizeof(uint32_t));
         *reason = XWB_SYNC_REASON_PROBE_FAILED;
         return false;
     }
@@ -181,25 +187,27 @@ RaceParams race_params(xwb_sim *s) {
     return p;
 }
 
-// a launch that may reset envs writes its per-workgroup counts (xwb_done_count reports the last such launch)
-template <typename P>
-void take_reset_counter(xwb_sim *s, P &p) { p.reset_partial = s->d_reset_partial; }
-
-// reset for the simple games: one launch, mode selects the envs
-int simple_reset(xwb_sim *s, int mode, const uint8_t *mask, hipStream_t st) {
-    timer_begin(s, s->t_reset, st);
+// The simple games' one kernel: `n_steps` steps (MODE_STEP; `autoreset`: finished envs start their next episode inside it) or a
+// reset of the envs `mode` selects.  A launch that may reset envs writes its per-workgroup counts (xwb_done_count reports the
+// last such launch).
+int simple_launch(xwb_sim *s, int mode, const uint8_t *mask, const int32_t *actions, int32_t act_rep, bool autoreset, int32_t n_steps,
+                  hipStream_t st) {
+    KernelTimer &t = mode == MODE_STEP ? s->t_step : s->t_reset;
+    auto fill = [&](auto &p) {
+        p.mode = mode; p.mask = mask; p.actions = actions; p.act_rep = act_rep; p.auto_reset = autoreset ? 1 : 0; p.n_steps = n_steps;
+        if (mode != MODE_STEP || autoreset) p.reset_partial = s->d_reset_partial;
+    };
+    timer_begin(s, t, st);
     if (s->cfg.game == XWB_SIMPLE_GAME) {
         SgParams p = sg_params(s);
-        p.mode = mode; p.mask = mask;
-        take_reset_counter(s, p);
+        fill(p);
         HIP_TRY(launch_simple_game(p, st));
     } else {
         RaceParams p = race_params(s);
-        p.mode = mode; p.mask = mask;
-        take_reset_counter(s, p);
+        fill(p);
         HIP_TRY(launch_simple_race(p, st));
     }
-    timer_end(s, s->t_reset, st);
+    timer_end(s, t, st);
     return XWB_OK;
 }
 
@@ -221,19 +229,47 @@ XwParams xw_params(xwb_sim *s) {
 // the reset kernel's parameters for a pre-generation pass: episode[e] + 1 of the listed envs into the shadow arrays
 XwParams shadow_params(xwb_sim *s) {
     XwParams q = xw_params(s);
-    q.shadow = 1; q.auto_reset = 1; q.sig_epoch = 0; q.wait_epoch = 0; q.packed = nullptr;
+    q.shadow = 1; q.auto_reset = AUTO_RESET_KEEP; q.sig_epoch = 0; q.wait_epoch = 0; q.packed = nullptr;
     q.grid = s->d_sh_grid; q.agent_xy = s->d_sh_agent; q.task_state = s->d_sh_task_state; q.task_state2 = s->d_sh_task_state2;
     q.sent_names = s->d_sh_sent_names; q.cand2d = s->d_sh_cand2d; q.goal_cells = s->d_sh_goal_cells;
     return q;
 }
 
+// ---- hand-overs between the caller's queue and the internal one ----
+// A hand-over is a sync word (epochs) and the event that stands in for it when the call hands over through events.
+struct HandOver { SyncSlot slot; hipEvent_t xwb_sim::*ev; };
+const HandOver STEP_DONE{SYNC_STEP, &xwb_sim::ev_step};
+const HandOver RESET_DONE{SYNC_RESET, &xwb_sim::ev_reset};
+const HandOver REGEN_DONE{SYNC_REGEN, &xwb_sim::ev_reset};
+const HandOver SPAN_CELLS_DONE{SYNC_SPAN_CELLS, &xwb_sim::ev_cells};
+const HandOver TERM_DONE{SYNC_SPAN_TERM, &xwb_sim::ev_term};
+
+// publish `h` on queue `q`: behind the work queued there so far (a one-thread signal kernel, or an event record)
+int publish(xwb_sim *s, const HandOver &h, bool by_epoch, uint32_t epoch, hipStream_t q) {
+    if (by_epoch) HIP_TRY(launch_xw_signal(s->d_sync + h.slot, epoch, q));
+    else HIP_TRY(hipEventRecord(s->*h.ev, q));
+    return XWB_OK;
+}
+
+// order the work queued on `q` from here on after `h` (a one-wavefront waiter under the batch's watchdog, or an event wait)
+int order_after(xwb_sim *s, const HandOver &h, bool by_epoch, uint32_t epoch, hipStream_t q) {
+    if (by_epoch) HIP_TRY(launch_xw_wait(s->d_sync + h.slot, epoch, s->d_sync + SYNC_POISON, s->xw.poison_host, q));
+    else HIP_TRY(hipStreamWaitEvent(q, s->*h.ev, 0));
+    return XWB_OK;
+}
+
+void step_record_invalidate(xwb_sim *s) {
+    s->rec.path = XWB_PATH_NONE;
+    s->rec.step_pub_queued = false;
+    s->shadow_ok = false; s->regen_pending = false; s->regen_deferred = false; s->snap_ok = false;
+}
+
 // A regeneration pass of xwb_step_autoreset may still be reading the done list and the episode counters on the side queue:
 // every other verb that touches them orders `st` behind it first (the next xwb_step_autoreset waits inside its step kernel).
 int join_regen(xwb_sim *s, hipStream_t st) {
-    { const int rcf = flush_regen(s); if (rcf) return rcf; }
+    XWB_TRY(flush_regen(s));
     if (!s->regen_pending) return XWB_OK;
-    if (s->regen_by_epoch) HIP_TRY(launch_xw_wait(s->d_sync + 8, s->epoch_regen, s->d_sync + 4, s->xw.poison_host, st));
-    else HIP_TRY(hipStreamWaitEvent(st, s->ev_reset, 0));
+    XWB_TRY(order_after(s, REGEN_DONE, s->regen_by_epoch, s->epoch_regen, st));
     s->regen_pending = false;
     return XWB_OK;
 }
@@ -242,28 +278,26 @@ int join_regen(xwb_sim *s, hipStream_t st) {
 // just started), into the free shadow slots, on the internal queue behind that step's kernel.
 int launch_regen(xwb_sim *s, bool by_epoch) {
     XwParams q = shadow_params(s);
-    if (by_epoch) HIP_TRY(launch_xw_wait(s->d_sync + 1, s->epoch_step, s->d_sync + 4, s->xw.poison_host, s->side));
-    else HIP_TRY(hipStreamWaitEvent(s->side, s->ev_step, 0));
+    XWB_TRY(order_after(s, STEP_DONE, by_epoch, s->epoch_step, s->side));
     timer_begin(s, s->t_reset, s->side);
     HIP_TRY(launch_xw_reset(q, MODE_RESET_DONE, s->side));
     timer_end(s, s->t_reset, s->side);
     if (by_epoch) {
         s->epoch_regen_prev = s->epoch_regen; s->regen_seq_prev = s->regen_seq; s->regen_seq = s->step_seq;
-        if (++s->epoch_regen == 0) s->epoch_regen = 1;
-        HIP_TRY(launch_xw_signal(s->d_sync + 8, s->epoch_regen, s->side));
-    } else {
-        HIP_TRY(hipEventRecord(s->ev_reset, s->side));
+        next_epoch(s->epoch_regen);
     }
+    XWB_TRY(publish(s, REGEN_DONE, by_epoch, s->epoch_regen, s->side));
     s->regen_pending = true; s->regen_by_epoch = by_epoch;
     return XWB_OK;
 }
 
 // ... which xwb_reset_done leaves to the next verb after a fused step (see there): every verb that steps, or that touches what
 // the pass reads or writes (join_regen), queues it first -- with the list and counter of the step it belongs to still current
+// (and its hand-over mode: only a step call changes s->rec.epochs, after this)
 int flush_regen(xwb_sim *s) {
     if (!s->regen_deferred) return XWB_OK;
     s->regen_deferred = false;
-    return launch_regen(s, s->regen_deferred_by_epoch);
+    return launch_regen(s, s->rec.epochs);
 }
 
 // xworld: reset the compacted list (or all), then re-render those envs.
@@ -271,130 +305,186 @@ int flush_regen(xwb_sim *s) {
 // the (latency-bound, two-wavefront) reset kernel then runs on the side stream as soon as the step kernel is
 // done, i.e. *beside* render_all.  render_all may read grid rows of finished envs while they are being
 // regenerated; those envs' frames are rewritten in full by render(list) below, which waits for both.
-int xw_reset_list(xwb_sim *s, int mode, bool keep_done, bool render, hipStream_t st, bool beside_render) {
-    { const int rcj = join_regen(s, st); if (rcj) return rcj; }
-    if (render) { s->frame_src = mode == MODE_RESET_ALL ? 0 : 2; s->draws_since_pack += 1; }
+int xw_reset_list(xwb_sim *s, int mode, hipStream_t st, bool beside_render = false) {
+    XWB_TRY(join_regen(s, st));
+    s->frame_src = mode == MODE_RESET_ALL ? PACK_SRC_LIVE : PACK_SRC_LIST;
+    s->draws_since_pack += 1;
     if (s->shadow_ok) s->shadow_breaks += 1;
     s->shadow_ok = false;                  // the episodes these envs start now are the ones their shadows held
     s->snap_ok = false;                    // ... and the live grids are rewritten without the snapshot
     XwParams p = xw_params(s);
-    // 0: the reset kernel clears the done codes; 1: they are kept (step_autoreset); 2: the reset runs on the side stream
-    // beside work already queued on `st` that may still read this step's codes -> the list render, which is ordered
-    // on `st` after that work, clears them instead
-    p.auto_reset = keep_done ? 1 : (beside_render && render ? 2 : 0);
+    // beside work already queued on `st` that may still read this step's codes: the list render, ordered on `st` after that
+    // work, clears them
+    p.auto_reset = beside_render ? AUTO_RESET_BY_LIST : AUTO_RESET_CLEAR;
     hipStream_t rs = beside_render ? s->side : st;
-    const bool span_sync = beside_render && s->span_step && xw_ego_span(p);
-    // full observation: the two queues hand over through epochs in device memory (XwParams::sync) -- the side queue's
-    // kernel waits for the step kernel's epoch, the list render for the reset kernel's; no event / barrier packets.
-    // The mode is the one the step call chose (s->step_epochs): its kernels are the publishers, already enqueued.
-    const bool by_epoch = s->step_epochs && beside_render && render && !p.visible_radius && mode != MODE_RESET_ALL;
-    if (by_epoch) {
-        HIP_TRY(launch_xw_wait(s->d_sync + 1, s->epoch_step, s->d_sync + 4, p.poison_host, s->side));
-        if (++s->epoch_reset == 0) s->epoch_reset = 1;
-    } else if (beside_render) {
-        // (span path: the map generator only has to wait for the kernel that reads the grids; the goal images are redrawn
-        // once the kernels that evaluate pixels from them are through)
-        if (span_sync && s->span_epochs) HIP_TRY(launch_xw_wait(s->d_sync + 5, s->epoch_step, s->d_sync + 4, p.poison_host, s->side));
-        else HIP_TRY(hipStreamWaitEvent(s->side, span_sync ? s->ev_cells : s->ev_step, 0));
-    }
-    // (span path with a list render to follow: the goal images are redrawn by that render's first launch, beside the cell tables)
-    const bool split = span_sync && render && mode != MODE_RESET_ALL;
+    // egocentric span path: the map generator only has to wait for the kernel that reads the grids; the goal images are redrawn
+    // by the list render's first launch, beside the cell tables, once the step's term gather is through (it shares their buffers)
+    const bool split = beside_render && s->rec.path == XWB_PATH_EGO_SPAN;
+    const bool span_epochs = split && s->rec.epochs;
+    // full observation: the side queue's kernel waits for the step kernel's epoch, the list render for the reset kernel's; the
+    // publishers are the step call's kernels, already enqueued
+    const bool by_epoch = beside_render && s->rec.epochs && s->rec.step_pub_queued && !p.visible_radius && mode != MODE_RESET_ALL;
+    if (beside_render) XWB_TRY(order_after(s, split ? SPAN_CELLS_DONE : STEP_DONE, by_epoch || span_epochs, s->epoch_step, s->side));
     timer_begin(s, s->t_reset, rs);
-    if (split) HIP_TRY(launch_xw_reset(p, mode, rs, nullptr, nullptr, 0, 1));
-    else if (span_sync && s->span_epochs) HIP_TRY(launch_xw_reset(p, mode, rs, nullptr, s->d_sync + 6, s->epoch_step));
-    else HIP_TRY(launch_xw_reset(p, mode, rs, span_sync ? s->ev_step : nullptr));
+    HIP_TRY(launch_xw_reset(p, mode, rs));
+    if (p.visible_radius && !split) HIP_TRY(launch_xw_warp_goals(p, mode != MODE_RESET_ALL, rs));
     timer_end(s, s->t_reset, rs);
-    if (by_epoch) {
-        HIP_TRY(launch_xw_signal(s->d_sync + 3, s->epoch_reset, s->side));     // queued behind the reset kernel
-        p.wait_epoch = s->epoch_reset;
-        timer_begin(s, s->t_list, st);
-        HIP_TRY(launch_xw_render(p, 1, st));
-        timer_end(s, s->t_list, st);
-        return XWB_OK;
-    }
     if (split) {
-        // egocentric span path: the map generator and the front kernels of the new episodes' first frames run on the side
-        // queue, beside the big gather (they write nothing the caller reads).  They follow the step's term gather -- it shares
-        // their buffers -- which also puts them behind its evaluation kernel, the last reader of the old goal images.
-        // Only the short gather that stores those frames runs on the CALLER's stream: it overwrites the terminal frames, which
-        // work queued there before this call may still read (xwb.h xwb_reset_done).  (auto_reset == 2: that gather clears the codes.)
-        if (s->span_epochs) HIP_TRY(launch_xw_wait(s->d_sync + 7, s->epoch_step, s->d_sync + 4, p.poison_host, rs));
-        else HIP_TRY(hipStreamWaitEvent(rs, s->ev_term, 0));
-        HIP_TRY(launch_xw_render(p, 7, rs));                 // goal images + cell tables in one launch, then the evaluation
-        if (s->span_epochs) {
-            if (++s->epoch_reset == 0) s->epoch_reset = 1;
-            HIP_TRY(launch_xw_signal(s->d_sync + 3, s->epoch_reset, rs));
-            HIP_TRY(launch_xw_wait(s->d_sync + 3, s->epoch_reset, s->d_sync + 4, p.poison_host, st));
-        } else {
-            HIP_TRY(hipEventRecord(s->ev_reset, s->side));
-            HIP_TRY(hipStreamWaitEvent(st, s->ev_reset, 0));
-        }
-        timer_begin(s, s->t_list, st);
-        HIP_TRY(launch_xw_render(p, 6, st));
-        timer_end(s, s->t_list, st);
-        return XWB_OK;
+        // the map generator and the front kernels of the new episodes' first frames run on the side queue, beside the big
+        // gather (they write nothing the caller reads).  Only the short gather that stores those frames runs on the CALLER's
+        // stream: it overwrites the terminal frames, which work queued there before this call may still read (xwb.h xwb_reset_done).
+        XWB_TRY(order_after(s, TERM_DONE, span_epochs, s->epoch_step, rs));
+        HIP_TRY(launch_xw_render(p, RENDER_LIST_FRONT_WARP, rs));
     }
     if (beside_render) {
-        HIP_TRY(hipEventRecord(s->ev_reset, s->side));
-        HIP_TRY(hipStreamWaitEvent(st, s->ev_reset, 0));
+        const bool ep = by_epoch || span_epochs;
+        if (ep) next_epoch(s->epoch_reset);
+        XWB_TRY(publish(s, RESET_DONE, ep, s->epoch_reset, s->side));
+        if (by_epoch) p.wait_epoch = s->epoch_reset;                 // (the list render waits for it itself)
+        else XWB_TRY(order_after(s, RESET_DONE, ep, s->epoch_reset, st));
     }
-    if (render) {
-        if (mode == MODE_RESET_ALL) {
-            timer_begin(s, s->t_render, st);
-            HIP_TRY(launch_xw_render(p, 0, st));
-            timer_end(s, s->t_render, st);
-        } else {
-            timer_begin(s, s->t_list, st);
-            HIP_TRY(launch_xw_render(p, 1, st));
-            timer_end(s, s->t_list, st);
-        }
+    if (mode == MODE_RESET_ALL) {
+        timer_begin(s, s->t_render, st);
+        HIP_TRY(launch_xw_render(p, RENDER_ALL, st));
+        timer_end(s, s->t_render, st);
+    } else {
+        timer_begin(s, s->t_list, st);
+        HIP_TRY(launch_xw_render(p, split ? RENDER_LIST_GATHER : RENDER_LIST, st));
+        timer_end(s, s->t_list, st);
     }
+    return XWB_OK;
+}
+
+// What a step call runs, decided once at its top.
+struct StepPlan {
+    int path;          // XWB_PATH_*: the kernel sequence
+    bool epochs;       // the hand-overs are epochs: what xwb_create / xwb_queue_sync_mode found out about `st`; events for a
+                       // stream nobody probed (no verb synchronises the host by itself)
+    bool snaps;        // the step also writes the look-ahead snapshot for the next one (XwParams::snap_grid_out)
+};
+
+StepPlan choose_path(xwb_sim *s, const int32_t *actions_dev, int32_t act_rep, bool autoreset, hipStream_t st) {
+    StepPlan k{XWB_PATH_CLASSIC, use_epochs(s, st, false), false};
+    if (s->cfg.visible_radius) {
+        k.path = xw_ego_span(s->xw) ? XWB_PATH_EGO_SPAN : XWB_PATH_EGO_PER_ENV;
+    } else if (autoreset) {
+        // xwb_step_autoreset with pre-generated episodes (XwParams::swap_shadow): the step kernel starts the next episode of
+        // the envs it finishes, ONE render draws every env, the side queue regenerates the consumed shadows beside it
+        if (s->pregen) k.path = XWB_PATH_PREGEN;
+    } else if (s->pregen && s->shadow_breaks < 3 && !(s->cfg.debug_flags & XWB_DEBUG_NO_LAZY)) {
+        // ... and a plain step whose xwb_reset_done installs them (XwParams::list_swap): no terminal snapshot, the render reads
+        // the live grid.  Only while the caller's verbs leave the shadows alone (a loop of masked / single resets would pay a
+        // whole-batch regeneration per call: after a few such breaks the batch stays on the classic path).
+        // Under the built-in policy it also writes the grids as the NEXT step will leave them (XwParams::snap_grid_out); when the
+        // previous verbs kept such a snapshot current for exactly this step, this call is ONE launch: render blocks that draw from
+        // it, step blocks beside them.
+        k.snaps = s->d_snap_grid[0] != nullptr && actions_dev == nullptr;
+        const bool fused = k.snaps && s->snap_ok && s->snap_step == s->policy_step && s->snap_act_rep == act_rep && !s->draw_off;
+        k.path = fused ? XWB_PATH_LAZY_FUSED : XWB_PATH_LAZY;
+    }
+    return k;
+}
+
+bool is_lazy(int path) { return path == XWB_PATH_LAZY || path == XWB_PATH_LAZY_FUSED; }
+
+// XWB_PATH_PREGEN: every env from its live grid; the render publishes the step epoch, the regeneration pass follows it
+int step_pregen(xwb_sim *s, XwParams &p, bool epochs, hipStream_t st) {
+    if (!epochs) { p.sig_epoch = 0; XWB_TRY(publish(s, STEP_DONE, false, 0, st)); }
+    timer_begin(s, s->t_render, st);
+    HIP_TRY(launch_xw_render(p, RENDER_ALL, st));
+    timer_end(s, s->t_render, st);
+    return launch_regen(s, epochs);
+}
+
+// xwb_step_autoreset without pre-generated episodes: reset + first frame of the new episode of the finished envs on the side
+// stream, beside the render of everyone else; their terminal frames are not materialised.
+// Epochs (full observation, and the egocentric span path, whose cells kernel publishes the step epoch): the side queue's first
+// kernel waits for "step kernel complete", which the FIRST kernel of the render publishes; a one-wavefront kernel at the end of
+// this call waits for the side queue's.  The render is enqueued BEFORE the side queue's waiter (publisher first: xw_device.h),
+// and the side queue's signal before the final waiter.
+int step_autoreset_classic(xwb_sim *s, XwParams &p, bool epochs, bool span, hipStream_t st) {
+    const bool ep = epochs && (!p.visible_radius || span);
+    if (!ep) { p.sig_epoch = 0; XWB_TRY(publish(s, STEP_DONE, false, 0, st)); }
+    timer_begin(s, s->t_render, st);
+    HIP_TRY(launch_xw_render(p, RENDER_ALIVE, st));
+    timer_end(s, s->t_render, st);
+    XWB_TRY(order_after(s, STEP_DONE, ep, s->epoch_step, s->side));
+    if (ep) next_epoch(s->epoch_reset);
+    XwParams pr = xw_params(s);
+    pr.sig_epoch = 0; pr.auto_reset = AUTO_RESET_KEEP;
+    // (span path: the goal images of the reset envs are redrawn in the list render's first launch, beside their cell tables;
+    // nothing else reads them -- the big render's kernels skip the finished envs)
+    timer_begin(s, s->t_reset, s->side);
+    HIP_TRY(launch_xw_reset(pr, MODE_RESET_DONE, s->side));
+    if (pr.visible_radius && !span) HIP_TRY(launch_xw_warp_goals(pr, true, s->side));
+    timer_end(s, s->t_reset, s->side);
+    timer_begin(s, s->t_list, s->side);
+    HIP_TRY(launch_xw_render(pr, span ? RENDER_LIST_WARP : RENDER_LIST, s->side));
+    timer_end(s, s->t_list, s->side);
+    XWB_TRY(publish(s, RESET_DONE, ep, s->epoch_reset, s->side));      // queued behind the list render
+    return order_after(s, RESET_DONE, ep, s->epoch_reset, st);
+}
+
+// XWB_PATH_LAZY_FUSED: the step is complete when this kernel is: nothing publishes its epoch here -- xwb_reset_done's list
+// render does
+int step_fused(xwb_sim *s, XwParams &p, bool epochs, hipStream_t st) {
+    p.sig_epoch = 0;
+    timer_begin(s, s->t_render, st);
+    HIP_TRY(launch_xw_step_render(p, st));
+    timer_end(s, s->t_render, st);
+    if (!epochs) XWB_TRY(publish(s, STEP_DONE, false, 0, st));
+    return XWB_OK;
+}
+
+// xwb_step's render on the classic, lazy and egocentric paths.  Classic: finished envs keep a terminal snapshot of their grid
+// (step kernel) from which the big render draws their last frame, so a following xwb_reset_done can regenerate the live state
+// beside that render right away (lazy: nothing rewrites the live grid beside it).  The egocentric render reads more than the grid
+// (heading, goal images): there the terminal frames are rendered from the (short) list on the side stream, beside the big render,
+// which skips those envs; a following xwb_reset_done queues behind that list render.  On the span path (kernels_xworld_ego.hip)
+// only the front kernels read the env state: its hand-overs are published behind them, the terminal frames leave through a short
+// list gather and the big gather skips them.
+int step_plain(xwb_sim *s, XwParams &p, bool epochs, int path, hipStream_t st) {
+    const bool per_env = path == XWB_PATH_EGO_PER_ENV;
+    if (per_env || (!p.visible_radius && !epochs)) XWB_TRY(publish(s, STEP_DONE, false, 0, st));
+    if (per_env) {
+        XwParams pr = xw_params(s);
+        pr.sig_epoch = 0; pr.list_flag = 1; pr.ego_list_beside = 1;
+        XWB_TRY(order_after(s, STEP_DONE, false, 0, s->side));
+        HIP_TRY(launch_xw_render(pr, RENDER_LIST, s->side));
+        XWB_TRY(publish(s, TERM_DONE, false, 0, s->side));
+    }
+    timer_begin(s, s->t_render, st);
+    if (path == XWB_PATH_EGO_SPAN) {
+        p.list_flag = 1;
+        if (epochs) HIP_TRY(launch_xw_render(p, RENDER_SPAN_STEP, st));          // (p.sig_epoch: sync[SYNC_SPAN_*])
+        else HIP_TRY(launch_xw_render(p, RENDER_SPAN_STEP, st, s->ev_step, s->ev_term, s->ev_cells));
+    } else {
+        HIP_TRY(launch_xw_render(p, p.visible_radius ? RENDER_ALIVE : (is_lazy(path) ? RENDER_ALL : RENDER_ALL_TERM), st));
+    }
+    timer_end(s, s->t_render, st);
+    if (per_env) XWB_TRY(order_after(s, TERM_DONE, false, 0, st));
     return XWB_OK;
 }
 
 int do_step(xwb_sim *s, const int32_t *actions_dev, int32_t act_rep, bool autoreset, hipStream_t st) {
     if (act_rep < 1) return fail(XWB_ERR_ARG, "act_rep must be >= 1");
-    if (s->cfg.game == XWB_SIMPLE_GAME) {
-        SgParams p = sg_params(s);
-        p.actions = actions_dev; p.act_rep = act_rep; p.auto_reset = autoreset ? 1 : 0;
-        if (autoreset) take_reset_counter(s, p);
-        timer_begin(s, s->t_step, st);
-        HIP_TRY(launch_simple_game(p, st));
-        timer_end(s, s->t_step, st);
-    } else if (s->cfg.game == XWB_SIMPLE_RACE) {
-        RaceParams p = race_params(s);
-        p.actions = actions_dev; p.act_rep = act_rep; p.auto_reset = autoreset ? 1 : 0;
-        if (autoreset) take_reset_counter(s, p);
-        timer_begin(s, s->t_step, st);
-        HIP_TRY(launch_simple_race(p, st));
-        timer_end(s, s->t_step, st);
+    if (s->cfg.game != XWB_XWORLD2D) {
+        XWB_TRY(simple_launch(s, MODE_STEP, nullptr, actions_dev, act_rep, autoreset, 1, st));
     } else {
-        // hand-over mode of this call: what xwb_create / xwb_queue_sync_mode found out about `st`; events for a stream
-        // nobody probed (no verb synchronises the host by itself)
-        { const int rcf = flush_regen(s); if (rcf) return rcf; }
-        const bool epochs = use_epochs(s, st, false);
-        s->step_epochs = epochs;
-        // xwb_step_autoreset with pre-generated episodes (XwParams::swap_shadow): the step kernel starts the next episode of
-        // the envs it finishes, ONE render draws every env, the side queue regenerates the consumed shadows beside it
-        const bool pregen = autoreset && s->pregen;
-        // ... and a plain step whose xwb_reset_done installs them (XwParams::list_swap): no terminal snapshot, the render reads
-        // the live grid.  Only while the caller's verbs leave the shadows alone (a loop of masked / single resets would pay a
-        // whole-batch regeneration per call: after a few such breaks the batch stays on the classic path).
-        const bool lazy = !autoreset && s->pregen && s->shadow_breaks < 3 && !(s->cfg.debug_flags & XWB_DEBUG_NO_LAZY);
+        XWB_TRY(flush_regen(s));
+        const StepPlan k = choose_path(s, actions_dev, act_rep, autoreset, st);
+        const bool lazy = is_lazy(k.path), pregen = k.path == XWB_PATH_PREGEN;
         if (pregen || lazy) {
             if (!s->shadow_ok) {               // first use, or another verb reset envs since: make every env's next episode
-                { const int rcj = join_regen(s, st); if (rcj) return rcj; }
+                XWB_TRY(join_regen(s, st));
                 HIP_TRY(launch_xw_reset(shadow_params(s), MODE_RESET_ALL, st));
                 s->shadow_ok = true;
             } else if (s->regen_pending && !s->regen_by_epoch) {
-                HIP_TRY(hipStreamWaitEvent(st, s->ev_reset, 0));      // (events: the step kernel cannot wait for itself)
-                s->regen_pending = false;
+                XWB_TRY(join_regen(s, st));    // (events: the step kernel cannot wait for itself)
             }
         } else {
-            const int rcj = join_regen(s, st);
-            if (rcj) return rcj;
+            XWB_TRY(join_regen(s, st));
         }
-        s->step_lazy = lazy;
         s->count_sel = (s->count_sel + 1) % 3; // this step appends to the counter the previous one zeroed ...
         s->list_sel ^= 1;                      // ... and to the list the one before it filled
         s->step_seq += 1;
@@ -406,17 +496,13 @@ int do_step(xwb_sim *s, const int32_t *actions_dev, int32_t act_rep, bool autore
             p.swap_shadow = 2;
             p.regen_wait = !s->regen_pending || !s->regen_by_epoch ? 0u : (s->regen_seq + 2 <= s->step_seq ? s->epoch_regen : s->epoch_regen_prev);
         }
-        // A lazy step under the built-in policy also writes the grids as the NEXT step will leave them (XwParams::snap_grid_out);
-        // when the previous verbs kept such a snapshot current for exactly this step, this call is ONE launch: render blocks that
-        // draw from it, step blocks beside them (XWB_PATH_LAZY_FUSED).
-        const bool snaps = lazy && s->d_snap_grid[0] != nullptr && actions_dev == nullptr;
-        const bool fused = snaps && s->snap_ok && s->snap_step == s->policy_step && s->snap_act_rep == act_rep && !s->draw_off;
-        if (snaps) {
+        const bool fused = k.path == XWB_PATH_LAZY_FUSED;
+        if (k.snaps) {
             p.snap_grid_out = s->d_snap_grid[s->snap_sel ^ 1];
             if (fused) p.snap_grid_in = s->d_snap_grid[s->snap_sel];
         }
-        if (++s->epoch_step == 0) s->epoch_step = 1;
-        p.sig_epoch = epochs ? s->epoch_step : 0;   // published by the render kernel queued behind the step kernel
+        const uint32_t epoch = next_epoch(s->epoch_step);
+        p.sig_epoch = k.epochs ? epoch : 0;    // published by the kernel behind the step kernel
         if (!fused) {
             timer_begin(s, s->t_step, st);
             HIP_TRY(launch_xw_step(p, st));
@@ -424,119 +510,23 @@ int do_step(xwb_sim *s, const int32_t *actions_dev, int32_t act_rep, bool autore
             if (p.idle_list) HIP_TRY(launch_xw_idle3d(p, st));
             timer_end(s, s->t_step, st);
         }
-        if (snaps) s->snap_sel ^= 1;
-        s->snap_ok = snaps;
+        if (k.snaps) s->snap_sel ^= 1;
+        s->snap_ok = k.snaps;
         s->snap_step = s->policy_step + 1u;
         s->snap_act_rep = act_rep;
-        s->step_fused = fused;
-        s->list_valid = true;
-        XwParams pr = xw_params(s);
-        pr.sig_epoch = 0;
-        const bool span = xw_ego_span(p);
-        if (pregen) {
-            if (!epochs) { p.sig_epoch = 0; HIP_TRY(hipEventRecord(s->ev_step, st)); }
-            timer_begin(s, s->t_render, st);
-            HIP_TRY(launch_xw_render(p, 0, st));                     // every env from its live grid; publishes the step epoch
-            timer_end(s, s->t_render, st);
-            XwParams q = shadow_params(s);
-            if (epochs) HIP_TRY(launch_xw_wait(s->d_sync + 1, s->epoch_step, s->d_sync + 4, p.poison_host, s->side));
-            else HIP_TRY(hipStreamWaitEvent(s->side, s->ev_step, 0));
-            timer_begin(s, s->t_reset, s->side);
-            HIP_TRY(launch_xw_reset(q, MODE_RESET_DONE, s->side));
-            timer_end(s, s->t_reset, s->side);
-            if (epochs) {
-                s->epoch_regen_prev = s->epoch_regen; s->regen_seq_prev = s->regen_seq; s->regen_seq = s->step_seq;
-                if (++s->epoch_regen == 0) s->epoch_regen = 1;
-                HIP_TRY(launch_xw_signal(s->d_sync + 8, s->epoch_regen, s->side));
-            } else {
-                HIP_TRY(hipEventRecord(s->ev_reset, s->side));
-            }
-            s->regen_pending = true; s->regen_by_epoch = epochs;
-            s->list_valid = false;
-        } else if (autoreset) {
-            // Finished envs: reset + first frame of the new episode on the side stream, beside the render of everyone else;
-            // their terminal frames are not materialised.
-            // Epochs (full observation, and the egocentric span path, whose cells kernel publishes the step epoch): the side
-            // queue's first kernel waits for "step kernel complete", which the FIRST kernel of the render publishes; a
-            // one-wavefront kernel at the end of this call waits for the side queue's.  The render is enqueued BEFORE the
-            // side queue's waiter (publisher first: xw_device.h), and the side queue's signal before the final waiter.
-            const bool auto_epochs = epochs && (!p.visible_radius || span);
-            if (!auto_epochs) { p.sig_epoch = 0; HIP_TRY(hipEventRecord(s->ev_step, st)); }
-            timer_begin(s, s->t_render, st);
-            HIP_TRY(launch_xw_render(p, 2, st));
-            timer_end(s, s->t_render, st);
-            if (auto_epochs) {
-                HIP_TRY(launch_xw_wait(s->d_sync + 1, s->epoch_step, s->d_sync + 4, p.poison_host, s->side));
-                if (++s->epoch_reset == 0) s->epoch_reset = 1;
-            } else {
-                HIP_TRY(hipStreamWaitEvent(s->side, s->ev_step, 0));
-            }
-            pr.auto_reset = 1;
-            // (span path: the goal images of the reset envs are redrawn in the list render's first launch, beside their cell tables;
-            // nothing else reads them -- the big render's kernels skip the finished envs)
-            timer_begin(s, s->t_reset, s->side);
-            HIP_TRY(launch_xw_reset(pr, MODE_RESET_DONE, s->side, nullptr, nullptr, 0, span ? 1 : 0));
-            timer_end(s, s->t_reset, s->side);
-            timer_begin(s, s->t_list, s->side);
-            HIP_TRY(launch_xw_render(pr, span ? 8 : 1, s->side));
-            timer_end(s, s->t_list, s->side);
-            if (auto_epochs) {
-                HIP_TRY(launch_xw_signal(s->d_sync + 3, s->epoch_reset, s->side));      // queued behind the list render
-                HIP_TRY(launch_xw_wait(s->d_sync + 3, s->epoch_reset, s->d_sync + 4, p.poison_host, st));
-            } else {
-                HIP_TRY(hipEventRecord(s->ev_reset, s->side));
-                HIP_TRY(hipStreamWaitEvent(st, s->ev_reset, 0));
-            }
-            s->list_valid = false;
-        } else if (fused) {
-            // the step is complete when this kernel is: nothing publishes its epoch here -- xwb_reset_done's list render does
-            p.sig_epoch = 0;
-            timer_begin(s, s->t_render, st);
-            HIP_TRY(launch_xw_step_render(p, st));
-            timer_end(s, s->t_render, st);
-            if (!epochs) HIP_TRY(hipEventRecord(s->ev_step, st));
-        } else {
-            if (!p.visible_radius && !epochs) HIP_TRY(hipEventRecord(s->ev_step, st));
-            // Finished envs keep a terminal snapshot of their grid (step kernel) from which the big render draws their
-            // last frame, so a following xwb_reset_done can regenerate the live state beside that render right away.
-            // The egocentric render reads more than the grid (heading, goal images): there the terminal frames are
-            // rendered from the (short) list on the side stream, beside the big render, which skips those envs; a
-            // following xwb_reset_done queues behind that list render.
-            // On the span path (kernels_xworld_ego.hip) only the front kernels read the env state: ev_step is recorded
-            // behind them, the terminal frames leave through a short list gather (ev_term) and the big gather skips them.
-            if (p.visible_radius && !span) {
-                HIP_TRY(hipEventRecord(s->ev_step, st));
-                pr.list_flag = 1;
-                pr.ego_list_beside = 1;
-                HIP_TRY(hipStreamWaitEvent(s->side, s->ev_step, 0));
-                HIP_TRY(launch_xw_render(pr, 1, s->side));
-                HIP_TRY(hipEventRecord(s->ev_term, s->side));
-            }
-            timer_begin(s, s->t_render, st);
-            if (span) {
-                p.list_flag = 1;
-                s->span_epochs = epochs;
-                if (epochs) HIP_TRY(launch_xw_render(p, 4, st));          // (p.sig_epoch = this step's epoch: d_sync[5..7])
-                else HIP_TRY(launch_xw_render(p, 4, st, s->ev_step, s->ev_term, s->ev_cells));
-            } else {
-                HIP_TRY(launch_xw_render(p, p.visible_radius ? 2 : (lazy ? 0 : 3), st));     // (lazy: nothing rewrites the live grid beside it)
-            }
-            timer_end(s, s->t_render, st);
-            if (p.visible_radius && !span) HIP_TRY(hipStreamWaitEvent(st, s->ev_term, 0));
-        }
-    }
-    s->span_step = !autoreset && xw_ego_span(s->xw);
-    // sync[1] = this call's epoch once its step kernel is complete: published by render_all's first thread on every full-observation
-    // path that hands over through epochs (the egocentric paths publish other slots, or record events)
-    s->results_by_epoch = s->cfg.game == XWB_XWORLD2D && s->step_epochs && !s->cfg.visible_radius;
-    s->step_pub_queued = !s->step_fused;
-    s->last_path = s->cfg.game != XWB_XWORLD2D ? XWB_PATH_NONE :
-                   (s->cfg.visible_radius ? (xw_ego_span(s->xw) ? XWB_PATH_EGO_SPAN : XWB_PATH_EGO_PER_ENV) :
-                    (autoreset && s->pregen ? XWB_PATH_PREGEN : (s->step_lazy ? (s->step_fused ? XWB_PATH_LAZY_FUSED : XWB_PATH_LAZY) : XWB_PATH_CLASSIC)));
-    if (s->cfg.game == XWB_XWORLD2D) {     // a plain step on the classic path drew the finished envs from their terminal snapshots
-        s->frame_src = (!autoreset && !s->step_lazy && !s->cfg.visible_radius) ? 1 : 0;
+        if (pregen) XWB_TRY(step_pregen(s, p, k.epochs, st));
+        else if (autoreset) XWB_TRY(step_autoreset_classic(s, p, k.epochs, k.path == XWB_PATH_EGO_SPAN, st));
+        else if (fused) XWB_TRY(step_fused(s, p, k.epochs, st));
+        else XWB_TRY(step_plain(s, p, k.epochs, k.path, st));
+        s->list_valid = !autoreset;
+        s->rec.path = k.path;
+        s->rec.epochs = k.epochs;
+        s->rec.step_pub_queued = !fused;
+        // (a plain step on the classic path drew the finished envs from their terminal snapshots)
+        s->frame_src = k.path == XWB_PATH_CLASSIC && !autoreset ? PACK_SRC_TERM : PACK_SRC_LIVE;
         s->draws_since_pack += 1;
     }
+    s->last_path = s->rec.path;
     s->policy_step += 1;
     s->packed_pos += 1;
     s->autoreset_done = autoreset;
@@ -554,9 +544,9 @@ int xwb_reset(xwb_sim *s, void *stream) {
     XWB_LIVE(s);
     hipStream_t st = as_stream(stream);
     s->autoreset_done = false;
-    if (s->cfg.game != XWB_XWORLD2D) return simple_reset(s, MODE_RESET_ALL, nullptr, st);
+    if (s->cfg.game != XWB_XWORLD2D) return simple_launch(s, MODE_RESET_ALL, nullptr, nullptr, 1, false, 1, st);
     s->list_valid = false;
-    return xw_reset_list(s, MODE_RESET_ALL, false, true, st);
+    return xw_reset_list(s, MODE_RESET_ALL, st);
 }
 
 int xwb_reset_done(xwb_sim *s, void *stream) {
@@ -571,44 +561,45 @@ int xwb_reset_done(xwb_sim *s, void *stream) {
         HIP_TRY(hipMemsetAsync(s->d_done, 0, (size_t)s->n, st));
         return XWB_OK;
     }
-    if (s->cfg.game != XWB_XWORLD2D) return simple_reset(s, MODE_RESET_DONE, nullptr, st);
+    if (s->cfg.game != XWB_XWORLD2D) return simple_launch(s, MODE_RESET_DONE, nullptr, nullptr, 1, false, 1, st);
     if (!s->list_valid) {                      // no step since the last reset: rebuild the list from done[]
-        { const int rcj = join_regen(s, st); if (rcj) return rcj; }
+        XWB_TRY(join_regen(s, st));
         XwParams p = xw_params(s);
         HIP_TRY(hipMemsetAsync(p.done_count, 0, sizeof(int32_t), st));
         HIP_TRY(launch_xw_compact(p, MODE_RESET_DONE, st));
     }
-    if (s->list_valid && s->step_lazy && s->shadow_ok) {
+    const bool lazy = is_lazy(s->rec.path), fused = s->rec.path == XWB_PATH_LAZY_FUSED;
+    if (s->list_valid && lazy && s->shadow_ok) {
         // the step kept no terminal snapshot and every env's next episode is pre-generated: the list render installs the
         // shadows of the finished envs and draws their first frames (st); the side queue regenerates what was consumed, for
         // nobody in particular -- the next holder of the done list waits for it device-side
         s->list_valid = false;
-        s->frame_src = 2; s->draws_since_pack += 1;
+        s->frame_src = PACK_SRC_LIST; s->draws_since_pack += 1;
         XwParams p = xw_params(s);
-        p.auto_reset = 2; p.list_swap = 1;
-        const bool by_epoch = s->step_epochs;
+        p.auto_reset = AUTO_RESET_BY_LIST; p.list_swap = 1;
+        const bool by_epoch = s->rec.epochs;
         // (the installs go to the live state AND to the snapshot of it that the next fused step draws from; after a fused step
         // this render is the first kernel behind the step in the caller's queue: it publishes that step's epoch)
         if (s->snap_ok) { p.snap_grid_out = s->d_snap_grid[s->snap_sel]; p.snap_act_rep = s->snap_act_rep; }
-        p.sig_epoch = s->step_fused && by_epoch ? s->epoch_step : 0;
-        if (p.sig_epoch) s->step_pub_queued = true;
-        if (s->regen_pending && !s->regen_by_epoch) { HIP_TRY(hipStreamWaitEvent(st, s->ev_reset, 0)); s->regen_pending = false; }
-        p.wait_slot = 8;
+        p.sig_epoch = fused && by_epoch ? s->epoch_step : 0;
+        if (p.sig_epoch) s->rec.step_pub_queued = true;
+        if (s->regen_pending && !s->regen_by_epoch) XWB_TRY(join_regen(s, st));
+        p.wait_slot = SYNC_REGEN;
         p.wait_epoch = s->regen_pending ? s->epoch_regen : 0;
         timer_begin(s, s->t_list, st);
-        HIP_TRY(launch_xw_render(p, 1, st));
+        HIP_TRY(launch_xw_render(p, RENDER_LIST, st));
         timer_end(s, s->t_list, st);
         // Behind a fused step + render launch the regeneration cannot start before this list render does (it publishes the step's
         // epoch), and nothing needs it before the next step call: it is queued at the top of that call (flush_regen), where it
         // runs beside the render exactly as it would from here -- but a caller that synchronises the device after this verb
         // does not wait 70 us for pre-generated episodes nobody has asked for yet.
-        if (s->step_fused) { s->regen_deferred = true; s->regen_deferred_by_epoch = by_epoch; return XWB_OK; }
+        if (fused) { s->regen_deferred = true; return XWB_OK; }
         return launch_regen(s, by_epoch);
     }
     // (a lazy step's render reads the live grid: the classic reset may not rewrite it beside that render)
-    const bool beside = s->list_valid && !s->step_lazy;
+    const bool beside = s->list_valid && !lazy;
     s->list_valid = false;
-    return xw_reset_list(s, MODE_RESET_DONE, false, true, st, beside);
+    return xw_reset_list(s, MODE_RESET_DONE, st, beside);
 }
 
 int xwb_reset_masked(xwb_sim *s, const uint8_t *mask_dev, void *stream) {
@@ -616,14 +607,14 @@ int xwb_reset_masked(xwb_sim *s, const uint8_t *mask_dev, void *stream) {
     XWB_ON_DEVICE(s);
     XWB_LIVE(s);
     hipStream_t st = as_stream(stream);
-    if (s->cfg.game != XWB_XWORLD2D) return simple_reset(s, MODE_RESET_MASK, mask_dev, st);
-    { const int rcj = join_regen(s, st); if (rcj) return rcj; }
+    if (s->cfg.game != XWB_XWORLD2D) return simple_launch(s, MODE_RESET_MASK, mask_dev, nullptr, 1, false, 1, st);
+    XWB_TRY(join_regen(s, st));
     XwParams p = xw_params(s);
     p.mask = mask_dev;
     HIP_TRY(hipMemsetAsync(p.done_count, 0, sizeof(int32_t), st));
     HIP_TRY(launch_xw_compact(p, MODE_RESET_MASK, st));
     s->list_valid = false;
-    return xw_reset_list(s, MODE_RESET_MASK, false, true, st);
+    return xw_reset_list(s, MODE_RESET_MASK, st);
 }
 
 int xwb_reset_env(xwb_sim *s, int32_t env, void *stream) {
@@ -677,19 +668,7 @@ int xwb_step_n(xwb_sim *s, int32_t n_steps, int32_t act_rep, void *stream) {
         }
         return XWB_OK;
     }
-    timer_begin(s, s->t_step, st);
-    if (s->cfg.game == XWB_SIMPLE_GAME) {
-        SgParams p = sg_params(s);
-        p.actions = nullptr; p.act_rep = act_rep; p.auto_reset = 1; p.n_steps = n_steps;
-        take_reset_counter(s, p);
-        HIP_TRY(launch_simple_game(p, st));
-    } else {
-        RaceParams p = race_params(s);
-        p.actions = nullptr; p.act_rep = act_rep; p.auto_reset = 1; p.n_steps = n_steps;
-        take_reset_counter(s, p);
-        HIP_TRY(launch_simple_race(p, st));
-    }
-    timer_end(s, s->t_step, st);
+    XWB_TRY(simple_launch(s, MODE_STEP, nullptr, nullptr, act_rep, true, n_steps, st));
     s->policy_step += (uint32_t)n_steps;
     s->packed_pos += 1;
     s->autoreset_done = true;
@@ -722,7 +701,7 @@ int xwb_check_errors(xwb_sim *s, void *stream, int32_t *n_bad) {
     HIP_TRY(hipMemcpyAsync(n_bad, s->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemsetAsync(s->d_err, 0, sizeof(int32_t), st));
     uint32_t timed_out = 0;
-    if (s->d_sync) HIP_TRY(hipMemcpyAsync(&timed_out, s->d_sync + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (s->d_sync) HIP_TRY(hipMemcpyAsync(&timed_out, s->d_sync + SYNC_POISON, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (timed_out) s->poisoned = true;                 // sticky: the device word is never cleared
     XWB_LIVE(s);
@@ -742,7 +721,7 @@ int xwb_queue_sync_mode(xwb_sim *s, void *stream, int32_t *mode, int32_t *reason
 int xwb_step_path(xwb_sim *s, int32_t *path, int32_t *sync_mode, int32_t *shadow_breaks) {
     if (!s || !path) return fail(XWB_ERR_ARG, "NULL argument");
     *path = s->last_path;
-    if (sync_mode) *sync_mode = s->cfg.game == XWB_XWORLD2D ? (s->step_epochs ? XWB_QUEUE_SYNC_EPOCHS : XWB_QUEUE_SYNC_EVENTS) : XWB_QUEUE_SYNC_AUTO;
+    if (sync_mode) *sync_mode = s->cfg.game == XWB_XWORLD2D ? (s->rec.epochs ? XWB_QUEUE_SYNC_EPOCHS : XWB_QUEUE_SYNC_EVENTS) : XWB_QUEUE_SYNC_AUTO;
     if (shadow_breaks) *shadow_breaks = s->shadow_breaks;
     return XWB_OK;
 }
@@ -760,8 +739,8 @@ int xwb_debug_stall_handoff(xwb_sim *s, void *stream, int64_t budget_us) {
     if (!s->d_sync) return fail(XWB_ERR_STATE, "this game has no queue hand-off");
     if (budget_us < 1 || budget_us > 10000000) return fail(XWB_ERR_ARG, "budget_us must be in 1..10 000 000");
     XWB_ON_DEVICE(s);
-    // (slot 0 is the probe's; its tokens count up from 1, so this value is never reached)
-    HIP_TRY(launch_xw_wait(s->d_sync + 0, 0x7fffffffu, s->d_sync + 4, s->xw.poison_host, as_stream(stream), (unsigned long long)budget_us * 100ull));
+    // (the probe's slot: its tokens count up from 1, so this value is never reached)
+    HIP_TRY(launch_xw_wait(s->d_sync + SYNC_PROBE, 0x7fffffffu, s->d_sync + SYNC_POISON, s->xw.poison_host, as_stream(stream), (unsigned long long)budget_us * 100ull));
     return XWB_OK;
 }
 
@@ -788,15 +767,14 @@ extern "C" __attribute__((visibility("hidden"))) int xwb_internal_last_results(x
     if (s->packed_pos < 1) return fail(XWB_ERR_STATE, "no step has written the results ring yet");
     *rows = reinterpret_cast<const float *>(s->d_packed + (size_t)((s->packed_pos - 1) % s->packed_slots) * (size_t)s->n);
     *n = s->n;
-    hipStream_t bs = reinterpret_cast<hipStream_t>(beside);
-    const bool by_epoch = s->results_by_epoch && s->d_sync && s->step_pub_queued;   // (publisher first, waiter second: xw_device.h)
-    if (by_epoch) {
-        HIP_TRY(launch_xw_wait(s->d_sync + 1, s->epoch_step, s->d_sync + 4, s->xw.poison_host, bs));
-    } else {
+    // (the egocentric paths publish other slots, or record events; publisher first, waiter second: xw_device.h)
+    const bool by_epoch = s->rec.epochs && s->rec.step_pub_queued && !s->cfg.visible_radius;
+    const HandOver results{SYNC_STEP, &xwb_sim::ev_results};
+    if (!by_epoch) {
         if (!s->ev_results) HIP_TRY(hipEventCreateWithFlags(&s->ev_results, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(s->ev_results, as_stream(step_stream)));
-        HIP_TRY(hipStreamWaitEvent(bs, s->ev_results, 0));
+        XWB_TRY(publish(s, results, false, 0, as_stream(step_stream)));
     }
+    XWB_TRY(order_after(s, results, by_epoch, s->epoch_step, reinterpret_cast<hipStream_t>(beside)));
     return by_epoch ? 1 : 0;                                    // (>= 0: fine; 1 = nothing was enqueued on the caller's stream)
 }
 
@@ -848,7 +826,7 @@ int xwb_xw_render_grids(xwb_sim *s, const uint16_t *grids_dev, const uint8_t *fl
     q.fresh = const_cast<uint8_t *>(flags_dev);
     q.obs = static_cast<uint8_t *>(obs_dev);
     q.sig_epoch = 0; q.wait_epoch = 0; q.packed = nullptr; q.no_draw = 0;
-    HIP_TRY(launch_xw_render(q, 0, as_stream(stream)));
+    HIP_TRY(launch_xw_render(q, RENDER_ALL, as_stream(stream)));
     return XWB_OK;
 }
 
