@@ -67,13 +67,13 @@ def test_debug_env_override_is_read_once_per_process():
             "from xworld_amd.batched import BatchedSimulator\n"
             "s = BatchedSimulator('xworld', %r, num_envs=256)\n"
             "s.step(); print('PATH', s.step_path()['path'], s.ego_render_path)\n") % (ROOT, dict(OPTS, visible_radius=3))
-    for env, want in (({}, "PATH ego_span span"), ({"XWB_DEBUG": "ego_no_span,bogus_entry"}, "PATH ego_per_env per_env")):
+    for env, want in (({}, "PATH ego_span span"), ({"XWB_DEBUG": "ego_no_span,render_shape=64x2"}, "PATH ego_per_env per_env")):
         e = dict(os.environ)
         e.pop("XWB_DEBUG", None)
         e.update(env)
         r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=e, timeout=300)
         assert r.returncode == 0 and want in r.stdout, (r.stdout, r.stderr[-1500:])
-        assert ("unknown entry 'bogus_entry'" in r.stderr) == bool(env)
+        assert ("unknown entry 'render_shape=64x2'" in r.stderr) == bool(env)      # a removed launch-shape switch
 
 
 def test_streams_are_probed_only_on_request():

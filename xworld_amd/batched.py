@@ -75,9 +75,6 @@ class BatchedSimulator:
             if switch not in lib.DEBUG_FLAGS:
                 raise RuntimeError("unknown debug switch %r (one of %s)" % (switch, sorted(lib.DEBUG_FLAGS)))
             cfg.debug_flags |= lib.DEBUG_FLAGS[switch]
-        cfg.debug_ego_per = int(opts.get("debug_ego_per", 0))
-        cfg.debug_ego_pad = int(opts.get("debug_ego_pad", 0))
-        cfg.debug_render_shape = int(opts.get("debug_render_shape", 0))
         self.palette = None
         self._keep = []
         if name == "simple_game":

@@ -557,10 +557,15 @@ __device__ __forceinline__ uint4 xw_expand_chunk(const uint32_t *atlas, const ui
 // the side stream, so that render runs beside this kernel instead of after it.
 // ES = bytes per pixel: 1 = uint8 frames; 4 = float32 frames (pixel * 1/255, py_simulator.cpp:262-272) expanded from
 // a float copy of the tile table (628 KB, still L2-resident): the same kernel with 48-byte tile rows.
+// Launch shape of the whole-batch render (xw_render_all_kernel and the render blocks of xw_step_render_kernel): BS lanes
+// of PER 16-byte chunks each.  Measured on C4 / 8x8 / 11x11 (profiles/r1/render_shapes.txt): 128 x 2 is best everywhere
+// (8 KiB spans, up to 16 two-wave groups per CU); one chunk per lane leaves too few bytes per barrier, four too few groups
+// in flight.
+constexpr int XW_RENDER_BS = 128, XW_RENDER_PER = 2, XW_RENDER_SPAN = XW_RENDER_BS * XW_RENDER_PER;
 // LDS of one span: s_out4 [SPAN + PAD / 4 + TD / 4 + 1] uint4, s_code [SPAN * 16 / (144 * CH * ES) + 2 * XW_MAX_DIM^2] u16, s_done [NE]
-template <int CH, int BS, int PER, int ES>
+template <int CH, int ES>
 struct RenderLds {
-    static constexpr int SPAN = BS * PER, TD = 3 * ES, PAD = (TD + 3) / 4 * 4;
+    static constexpr int SPAN = XW_RENDER_SPAN, TD = 3 * ES, PAD = (TD + 3) / 4 * 4;
     static constexpr int OUT4 = SPAN + PAD / 4 + TD / 4 + 1;
     static constexpr int CODES = SPAN * 16 / (144 * CH * ES) + 2 * XW_MAX_DIM * XW_MAX_DIM;
     static constexpr int NE = SPAN * 16 / (144 * CH * ES) + 2;               // envs a span can touch
@@ -568,10 +573,10 @@ struct RenderLds {
 
 // One span (workgroup `blk`) of the whole-batch render.  SNAP (xw_step_render_kernel): the cell codes come from the look-ahead
 // snapshot the previous step left (p.snap_grid_in: the grids with THIS step's moves already applied).
-template <int DIM_T, int CH, bool CTX1, int BS, int PER, int RMODE, int ES, bool SNAP>
+template <int DIM_T, int CH, bool CTX1, int RMODE, int ES, bool SNAP>
 __device__ __forceinline__ void xw_render_span(const XwParams &p, const unsigned blk, uint4 *s_out4, uint16_t *s_code, uint8_t *s_done) {
     constexpr bool SKIP_DONE = RMODE == 2, TERM = RMODE == 3;
-    constexpr int SPAN = BS * PER;
+    constexpr int BS = XW_RENDER_BS, PER = XW_RENDER_PER, SPAN = XW_RENDER_SPAN;
     constexpr int TB = 12 * ES, TD = 3 * ES;                               // bytes / dwords per tile row
     constexpr int PAD = (TD + 3) / 4 * 4;                                   // dword index of the span's first chunk
     constexpr int IT = ((SPAN * 16 + TB - 1) / TB + 1 + BS - 1) / BS;       // tile rows per lane
@@ -662,16 +667,16 @@ __device__ __forceinline__ void xw_render_span(const XwParams &p, const unsigned
     }
 }
 
-template <int DIM_T, int CH, bool CTX1, int BS, int PER, int RMODE, int ES>
-__global__ __launch_bounds__(BS) void xw_render_all_kernel(XwParams p) {
-    typedef RenderLds<CH, BS, PER, ES> L;
+template <int DIM_T, int CH, bool CTX1, int RMODE, int ES>
+__global__ __launch_bounds__(XW_RENDER_BS) void xw_render_all_kernel(XwParams p) {
+    typedef RenderLds<CH, ES> L;
     __shared__ uint4 s_out4[L::OUT4];
     __shared__ uint16_t s_code[L::CODES];
     __shared__ uint8_t s_done[L::NE];
     // this kernel running = the step kernel queued before it is complete: tell the reset kernel's queue (xw_device.h)
     if (p.sig_epoch && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + SYNC_STEP, p.sig_epoch);
     if (p.no_draw) return;                                 // (xwb_xw_set_draw(sim, 0): launched with one workgroup, for the epoch)
-    xw_render_span<DIM_T, CH, CTX1, BS, PER, RMODE, ES, false>(p, blockIdx.x, s_out4, s_code, s_done);
+    xw_render_span<DIM_T, CH, CTX1, RMODE, ES, false>(p, blockIdx.x, s_out4, s_code, s_done);
 }
 
 // xwb_step of the default loop in ONE launch (XWB_PATH_LAZY_FUSED): blocks [0, step_blocks) step `epb` envs each (first
@@ -686,8 +691,8 @@ __host__ __device__ inline int xw_fused_epb(int max_dim) {
 }
 
 template <int DIM_T, int CH>
-__global__ __launch_bounds__(128, 8) void xw_step_render_kernel(XwParams p, int step_blocks) {
-    typedef RenderLds<CH, 128, 2, 1> L;
+__global__ __launch_bounds__(XW_RENDER_BS, 8) void xw_step_render_kernel(XwParams p, int step_blocks) {
+    typedef RenderLds<CH, 1> L;
     static_assert((L::OUT4 * 16 + L::CODES * 2 + L::NE + 15) / 16 * 16 <= XW_FUSED_LDS, "a span's staging must fit");
     __shared__ uint4 s_mem[XW_FUSED_LDS / 16];
     if ((int)blockIdx.x < step_blocks) {
@@ -696,8 +701,8 @@ __global__ __launch_bounds__(128, 8) void xw_step_render_kernel(XwParams p, int 
         return;
     }
     uint16_t *s_code = reinterpret_cast<uint16_t *>(s_mem + L::OUT4);
-    xw_render_span<DIM_T, CH, true, 128, 2, 0, 1, true>(p, blockIdx.x - (unsigned)step_blocks, s_mem, s_code,
-                                                          reinterpret_cast<uint8_t *>(s_code + L::CODES));
+    xw_render_span<DIM_T, CH, true, 0, 1, true>(p, blockIdx.x - (unsigned)step_blocks, s_mem, s_code,
+                                                reinterpret_cast<uint8_t *>(s_code + L::CODES));
 }
 
 // the compacted list of freshly reset envs, tile table through L1/L2.  A frame is cut into `parts` pieces of at most 512
@@ -792,25 +797,13 @@ __global__ __launch_bounds__(256) void xw_render_list_kernel(XwParams p, const i
     }
 }
 
-// render_all launch shape: xwb_config.debug_render_shape overrides the default (A/B switch)
-template <int DIM_T, int CH, int BS, int PER, int SKIP, int ES>
-static hipError_t render_all_shape(const XwParams &p, hipStream_t s) {
-    const unsigned long long n_chunks = (unsigned long long)p.n * (CH * 9 * ES * p.max_dim * p.max_dim);
-    const unsigned blocks = p.no_draw ? 1u : (unsigned)((n_chunks + BS * PER - 1) / (BS * PER));
-    if (p.context == 1) hipLaunchKernelGGL((xw_render_all_kernel<DIM_T, CH, true, BS, PER, SKIP, ES>), dim3(blocks), dim3(BS), 0, s, p);
-    else hipLaunchKernelGGL((xw_render_all_kernel<DIM_T, CH, false, BS, PER, SKIP, ES>), dim3(blocks), dim3(BS), 0, s, p);
-    return hipGetLastError();
-}
-
 template <int DIM_T, int CH, int SKIP, int ES>
 static hipError_t render_all(const XwParams &p, hipStream_t s) {
-    // measured on C4 / 8x8 / 11x11 (profiles/r1/render_shapes.txt): 128 x 2 is best everywhere (8 KiB spans, up to
-    // 16 two-wave groups per CU); one chunk per lane leaves too few bytes per barrier, four too few groups in flight
-    switch (p.dbg_render_shape) {                            // (xwb_config.debug_render_shape: A/B switch)
-        case 1: return render_all_shape<DIM_T, CH, 64, 2, SKIP, ES>(p, s);
-        case 2: return render_all_shape<DIM_T, CH, 256, 2, SKIP, ES>(p, s);
-        default: return render_all_shape<DIM_T, CH, 128, 2, SKIP, ES>(p, s);
-    }
+    const unsigned long long n_chunks = (unsigned long long)p.n * (CH * 9 * ES * p.max_dim * p.max_dim);
+    const unsigned blocks = p.no_draw ? 1u : (unsigned)((n_chunks + XW_RENDER_SPAN - 1) / XW_RENDER_SPAN);
+    if (p.context == 1) hipLaunchKernelGGL((xw_render_all_kernel<DIM_T, CH, true, SKIP, ES>), dim3(blocks), dim3(XW_RENDER_BS), 0, s, p);
+    else hipLaunchKernelGGL((xw_render_all_kernel<DIM_T, CH, false, SKIP, ES>), dim3(blocks), dim3(XW_RENDER_BS), 0, s, p);
+    return hipGetLastError();
 }
 
 template <int DIM_T, int CH>
@@ -818,8 +811,8 @@ static hipError_t step_render(const XwParams &p, hipStream_t s) {
     const unsigned long long n_chunks = (unsigned long long)p.n * (CH * 9 * p.max_dim * p.max_dim);
     const int epb = xw_fused_epb(p.max_dim);
     const int step_blocks = (p.n + epb - 1) / epb;
-    const unsigned blocks = (unsigned)step_blocks + (unsigned)((n_chunks + 255) / 256);
-    hipLaunchKernelGGL((xw_step_render_kernel<DIM_T, CH>), dim3(blocks), dim3(128), 0, s, p, step_blocks);
+    const unsigned blocks = (unsigned)step_blocks + (unsigned)((n_chunks + XW_RENDER_SPAN - 1) / XW_RENDER_SPAN);
+    hipLaunchKernelGGL((xw_step_render_kernel<DIM_T, CH>), dim3(blocks), dim3(XW_RENDER_BS), 0, s, p, step_blocks);
     return hipGetLastError();
 }
 

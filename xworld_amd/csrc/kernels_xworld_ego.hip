@@ -44,11 +44,7 @@ __device__ unsigned long long g_ego_prof2[12];     // stage stamps of the whole-
 #define EGO_T0()
 #define EGO_T(i)
 #define EGO_C0()
-#ifdef EGO_CELLS_STOP                                    // lab: the whole-batch cells kernel ends at stage i (wrong frames; for a kernel trace:
-#define EGO_C(i) do { if (!LIST && (i) == EGO_CELLS_STOP) return; } while (0)      // tools/lab/ego_cells_ablate.sh)
-#else
 #define EGO_C(i)
-#endif
 #endif
 
 struct EgoTap { int16_t s0, s1, w0, w1; };        // cv::resize: source indices and 11-bit weights of one output index
@@ -643,10 +639,12 @@ __device__ __forceinline__ void ego_wave_append(bool flag, uint32_t a, uint32_t 
 template <bool LIST> struct EgoCellsGeom { static constexpr int EPW = LIST ? 16 : 64; };
 // ALL_MISS (list of freshly reset envs whose goal images are being redrawn beside this: xw_ego_list_front_kernel): every goal
 // cell in view goes on the miss list, the cache bits are not looked at
-// NW: wavefronts per workgroup (they share the walk over the view cells of the same envs)
-template <int R, bool LIST, bool ALL_MISS, int NW = 4>
+// wavefronts per workgroup (they share the walk over the view cells of the same envs; 8 or 16 for the whole batch's 64 envs
+// measured no gain: profiles/r5)
+constexpr int EGO_CELLS_WAVES = 4;
+template <int R, bool LIST, bool ALL_MISS>
 __device__ __forceinline__ void ego_cells_body(const XwParams &p, const uint8_t *map, int skip_term, const int32_t *count_now, int bid, uint4 *smem4) {
-    constexpr int EPW = EgoCellsGeom<LIST>::EPW;
+    constexpr int EPW = EgoCellsGeom<LIST>::EPW, NW = EGO_CELLS_WAVES;
     const int D = p.max_dim, cells = D * D, tid = threadIdx.x, lane = tid & 63;
     uint16_t *s_code = reinterpret_cast<uint16_t *>(smem4);                // [EPW][cells]
     uint8_t *s_type = reinterpret_cast<uint8_t *>(s_code + EPW * cells);   // [EPW][cells] type of the entity in a cell, 3 = none
@@ -901,17 +899,12 @@ __device__ __forceinline__ void ego_cells_body(const XwParams &p, const uint8_t 
     EGO_C(6);
 }
 
-// (A/B hook -DEGO_CELLS_NW=8 | 16: the whole batch's workgroups with more wavefronts per 64 envs -- measured, no gain: profiles/r5)
-#ifndef EGO_CELLS_NW
-#define EGO_CELLS_NW 4
-#endif
-template <bool LIST> struct EgoCellsWaves { static constexpr int NW = LIST ? 4 : EGO_CELLS_NW; };
 template <int R, bool LIST>
-__global__ __launch_bounds__(64 * EgoCellsWaves<LIST>::NW) void xw_ego_cells_kernel(XwParams p, const uint8_t *map, int skip_term, const int32_t *count_now, int publish_step) {
+__global__ __launch_bounds__(64 * EGO_CELLS_WAVES) void xw_ego_cells_kernel(XwParams p, const uint8_t *map, int skip_term, const int32_t *count_now, int publish_step) {
     extern __shared__ uint4 smem4[];
     // (xwb_step_autoreset: this kernel running = the step kernel before it is complete; the reset's queue waits for that)
     if (publish_step && blockIdx.x == 0 && threadIdx.x == 0) xw_publish_epoch(p.sync + SYNC_STEP, p.sig_epoch);
-    ego_cells_body<R, LIST, false, EgoCellsWaves<LIST>::NW>(p, map, skip_term, count_now, (int)blockIdx.x, smem4);
+    ego_cells_body<R, LIST, false>(p, map, skip_term, count_now, (int)blockIdx.x, smem4);
 }
 
 // A cache entry [env][goal slot][view cell][heading] on the span path (EgoEntry): everything of the frame that blends this goal's
@@ -1767,6 +1760,16 @@ hipError_t launch_xw_ego_build_tab(const XwParams &p, hipStream_t s) {
 namespace {
 template <int CH, int R>
 hipError_t ego_span_render_list(const XwParams &p0, const EgoTables &t, hipStream_t s, int parts);
+// 16-byte chunks per lane of the whole-batch gather (the sweep of 2 | 4 | 8: profiles/NOTES.md, "Launch-shape sweep")
+constexpr int EGO_GATHER_PER = 4;
+// Bytes of LDS a whole-batch gather workgroup asks for on top of its own: 13 workgroups per CU instead of 16 -- the kernels
+// of a reset_done on the other queue (map generator, goal images, list render: 256-thread groups, up to 31 KB of LDS)
+// otherwise never find room beside this one and run after it (0.292 -> 0.271 ms per step on the C4-sized batch).
+template <int CH, int R, int ES>
+constexpr int ego_gather_pad() {
+    constexpr int lds = EgoSpanGeom<CH, R, ES, EGO_GATHER_PER>::LDS;
+    return 163840 / 13 - lds > 0 ? 163840 / 13 - lds : 0;
+}
 // mode 0 (RENDER_ALL): every env; 2 (RENDER_ALIVE): every env the last step did not finish (a reset runs beside this: their
 // state is in flux); 4 (RENDER_SPAN_STEP): a step's frames -- every env, the finished ones first and from the list (p.list_flag says how their context moves),
 //    ev_cells recorded once nothing reads the grids and agents any more (a reset's map generator may start), ev_front once
@@ -1780,34 +1783,25 @@ hipError_t ego_span_render(const XwParams &p, const EgoTables &t, int mode, hipS
     // mode 4 without events: the hand-overs to the reset's queue are epochs, published by the kernel that FOLLOWS the producer
     const int publish = mode == 4 && !ev_front && p.sig_epoch != 0;
     const size_t cells_lds = 64 * cells * 3 + ((p.n_icons + 15) & ~15) + ((p.n_icons + 2 + 15) & ~15);
-    hipLaunchKernelGGL((xw_ego_cells_kernel<R, false>), dim3((p.n + 63) / 64), dim3(64 * EgoCellsWaves<false>::NW), cells_lds, s, p, t.map, skip_front, nullptr, mode == 2 && p.sig_epoch != 0);
+    hipLaunchKernelGGL((xw_ego_cells_kernel<R, false>), dim3((p.n + 63) / 64), dim3(64 * EGO_CELLS_WAVES), cells_lds, s, p, t.map, skip_front, nullptr, mode == 2 && p.sig_epoch != 0);
     if (ev_cells) { const hipError_t e = hipEventRecord(ev_cells, s); if (e != hipSuccess) return e; }
-    const int nb_miss = p.dbg_ego_miss_blocks ? p.dbg_ego_miss_blocks : 4096;    // (a multiple of 4: up to four workgroups per goal cell)
-    hipLaunchKernelGGL((xw_ego_eval_kernel<CH, R>), dim3(nb_miss), dim3(256), 0, s, p, a4, t.lut, t.map, publish, t.comp);
+    // (a multiple of 4: up to four workgroups per goal cell; more never won -- profiles/r5/ego_miss_blocks_ab.txt)
+    hipLaunchKernelGGL((xw_ego_eval_kernel<CH, R>), dim3(4096), dim3(256), 0, s, p, a4, t.lut, t.map, publish, t.comp);
     if (ev_front) { const hipError_t e = hipEventRecord(ev_front, s); if (e != hipSuccess) return e; }
     const int es = p.obs_f32 ? 4 : 1;
     const unsigned long long n_chunks = (unsigned long long)p.n * (FB / (16 / es));
     const int32_t *cnt = (const int32_t *)p.done_count;
     const unsigned list_blocks = (unsigned)(p.n < 2048 ? p.n : 2048);
-    // A/B switches (xwb_config.debug_ego_per / debug_ego_pad): 16-byte chunks per lane (2 | 4 | 8), bytes of LDS a workgroup asks for on top of its own.
-    // Default padding: 13 workgroups per CU instead of 16 -- the kernels of a reset_done on the other queue (map generator,
-    // goal images, list render: 256-thread groups, up to 31 KB of LDS) otherwise never find room beside this one and run
-    // after it (0.292 -> 0.271 ms per step on the C4-sized batch).
-    const int per = p.dbg_ego_per ? p.dbg_ego_per : 4;
-    const int pad_env = p.dbg_ego_pad - 1;
-#define EGO_PAD(ESV, PERV) (pad_env >= 0 ? pad_env : (163840 / 13 - EgoSpanGeom<CH, R, ESV, PERV>::LDS > 0 ? 163840 / 13 - EgoSpanGeom<CH, R, ESV, PERV>::LDS : 0))
-#define EGO_GATHER_BIG(CTXV, ESV, PERV) hipLaunchKernelGGL((xw_ego_gather_kernel<CH, R, CTXV, ESV, PERV>), dim3((unsigned)((n_chunks + EGO_BS * PERV - 1) / (EGO_BS * PERV))), dim3(EGO_BS), EGO_PAD(ESV, PERV), s, p, skip_gather, publish)
 #define EGO_GATHER(CTXV, ESV) do { \
         if (mode == 4) { \
             hipLaunchKernelGGL((xw_ego_gather_list_kernel<CH, R, CTXV, ESV>), dim3(list_blocks * EgoSpanGeom<CH, R, ESV, 2>::SPE), dim3(EGO_BS), 0, s, p, cnt, publish); \
             if (ev_list) { const hipError_t e = hipEventRecord(ev_list, s); if (e != hipSuccess) return e; } \
         } \
-        if (per == 2) EGO_GATHER_BIG(CTXV, ESV, 2); else if (per == 8) EGO_GATHER_BIG(CTXV, ESV, 8); else EGO_GATHER_BIG(CTXV, ESV, 4); \
+        hipLaunchKernelGGL((xw_ego_gather_kernel<CH, R, CTXV, ESV, EGO_GATHER_PER>), dim3((unsigned)((n_chunks + EGO_BS * EGO_GATHER_PER - 1) / (EGO_BS * EGO_GATHER_PER))), \
+                           dim3(EGO_BS), (ego_gather_pad<CH, R, ESV>()), s, p, skip_gather, publish); \
     } while (0)
     if (p.context == 1) { if (es == 4) EGO_GATHER(true, 4); else EGO_GATHER(true, 1); }
     else { if (es == 4) EGO_GATHER(false, 4); else EGO_GATHER(false, 1); }
-#undef EGO_GATHER_BIG
-#undef EGO_PAD
 #undef EGO_GATHER
     return hipGetLastError();
 }
@@ -1874,7 +1868,7 @@ hipError_t ego_span_render_list(const XwParams &p0, const EgoTables &t, hipStrea
         // (parts & 4: the goal images of these envs are still to be redrawn -- the reset left them to this launch)
         const int nb_cells = (p.n + EPW - 1) / EPW;
         if (parts & 4) hipLaunchKernelGGL((xw_ego_list_front_kernel<R>), dim3(nb_cells + 4096), dim3(256), cells_lds, s, p, t.map, a4, cnt, nb_cells);
-        else hipLaunchKernelGGL((xw_ego_cells_kernel<R, true>), dim3(nb_cells), dim3(256), cells_lds, s, p, t.map, 0, cnt, 0);
+        else hipLaunchKernelGGL((xw_ego_cells_kernel<R, true>), dim3(nb_cells), dim3(64 * EGO_CELLS_WAVES), cells_lds, s, p, t.map, 0, cnt, 0);
         hipLaunchKernelGGL((xw_ego_eval_kernel<CH, R>), dim3(1024), dim3(256), 0, s, p, a4, t.lut, t.map, 0, t.comp);
     }
     if (!(parts & 2)) return hipGetLastError();

@@ -249,8 +249,8 @@ __device__ __forceinline__ void xw_store_chunk(uint4 *frame0, int cc, int chunks
 }
 
 // all envs: ONE-SHOT workgroups in dispatch order -- the store structure that reaches the write ceiling on this
-// chip (tools/render_lab.hip: one-shot 6.7 TB/s, every persistent / looping structure <= 5.7 TB/s; the persistent
-// LDS-table kernel this replaces ran at 4.4 TB/s).  Each workgroup owns SPAN = BS * PER consecutive 16-byte chunks
+// chip (the render lab, now in git history: one-shot 6.7 TB/s, every persistent / looping structure <= 5.7 TB/s; the persistent
+// LDS-table kernel this replaces ran at 4.4 TB/s).  Each workgroup owns XW_RENDER_SPAN consecutive 16-byte chunks
 // of the batch's frame bytes, cut at 1 KiB multiples of the global chunk index so every wavefront store is a whole
 // number of cache lines although env frames (7x7x3: 21 168 B) are not 128-byte aligned.  A frame row is a run of
 // 12-byte tile rows, so the span is assembled in LDS in OUTPUT order from 12-byte rows gathered from the tile table

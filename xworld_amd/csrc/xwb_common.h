@@ -350,9 +350,6 @@ struct XwParams {
     uint32_t sig_epoch, wait_epoch;
     int wait_slot;               // the list render's wait: a SyncSlot (SYNC_RESET: the reset kernel's epoch, SYNC_REGEN: the regeneration's)
     uint32_t *minstd;            // nullable: XWB_RNG_MINSTD, one libstdc++ minstd_rand0 state per env: the teacher's task draw
-    int dbg_ego_per, dbg_ego_pad, dbg_render_shape;   // xwb_config.debug_* (launch-shape A/B switches; 0 = defaults)
-    int dbg_ego_miss_blocks;     // XWB_DEBUG ego_miss_blocks=N: goal-cell workgroups of the whole-batch evaluation launch (0 = the default)
-                                 // (lab: frames wrong next to goals), bits 4.. its launch shape
     int no_draw;                 // xwb_xw_set_draw(sim, 0): the renders keep their bookkeeping (epochs, installs, fresh / done flags) and store no pixels
 };
 hipError_t launch_xw_step(const XwParams &p, hipStream_t s);

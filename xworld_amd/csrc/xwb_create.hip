@@ -22,34 +22,27 @@ const char *const POISON_MSG = "a device-side queue hand-off was not released wi
 namespace {
 
 // XWB_DEBUG (include/xwb.h, xwb_config "Debug configuration"): parsed once per process, OR-ed into every batch created
-struct DebugEnv { int32_t flags = 0, ego_per = 0, ego_pad = 0, render_shape = 0, ego_miss_blocks = 0; };
-const DebugEnv &debug_env() {
-    static const DebugEnv d = [] {
-        DebugEnv e;
+int32_t debug_env_flags() {
+    static const int32_t d = [] {
+        int32_t flags = 0;
         const char *v = getenv("XWB_DEBUG");
-        if (!v) return e;
+        if (!v) return flags;
         std::string all(v);
         size_t pos = 0;
         while (pos <= all.size()) {
             size_t end = all.find(',', pos);
             if (end == std::string::npos) end = all.size();
             const std::string t = all.substr(pos, end - pos);
-            if (t == "no_pregen") e.flags |= XWB_DEBUG_NO_PREGEN;
-            else if (t == "no_lazy") e.flags |= XWB_DEBUG_NO_LAZY;
-            else if (t == "ego_no_cache") e.flags |= XWB_DEBUG_EGO_NO_CACHE;
-            else if (t == "ego_no_span") e.flags |= XWB_DEBUG_EGO_NO_SPAN;
-            else if (t == "ego_no_flat") e.flags |= XWB_DEBUG_EGO_NO_FLAT;
-            else if (t == "no_fused") e.flags |= XWB_DEBUG_NO_FUSED;
-            else if (t.compare(0, 8, "ego_per=") == 0) e.ego_per = atoi(t.c_str() + 8);
-            else if (t.compare(0, 8, "ego_pad=") == 0) e.ego_pad = atoi(t.c_str() + 8) + 1;
-            else if (t.compare(0, 10, "ego_fused=") == 0) { fprintf(stderr, "xwb: XWB_DEBUG ego_fused: the fused lab kernel was removed (see profiles/NOTES.md)\n"); }
-            else if (t.compare(0, 16, "ego_miss_blocks=") == 0) { const int v = atoi(t.c_str() + 16); e.ego_miss_blocks = v >= 4 && v <= 65536 ? (v & ~3) : 0; }
-            else if (t == "render_shape=64x2") e.render_shape = 1;
-            else if (t == "render_shape=256x2") e.render_shape = 2;
+            if (t == "no_pregen") flags |= XWB_DEBUG_NO_PREGEN;
+            else if (t == "no_lazy") flags |= XWB_DEBUG_NO_LAZY;
+            else if (t == "ego_no_cache") flags |= XWB_DEBUG_EGO_NO_CACHE;
+            else if (t == "ego_no_span") flags |= XWB_DEBUG_EGO_NO_SPAN;
+            else if (t == "ego_no_flat") flags |= XWB_DEBUG_EGO_NO_FLAT;
+            else if (t == "no_fused") flags |= XWB_DEBUG_NO_FUSED;
             else if (!t.empty()) fprintf(stderr, "libxwb: XWB_DEBUG: unknown entry '%s' ignored\n", t.c_str());
             pos = end + 1;
         }
-        return e;
+        return flags;
     }();
     return d;
 }
@@ -362,8 +355,6 @@ int xw_setup(xwb_sim *s) {
     p.num_blocks = c.num_blocks; p.max_steps_factor = c.max_steps_factor; p.task_mode = c.task_mode;
     p.channels = ch; p.n_icons = c.n_icons;
     p.obs_f32 = f32 ? 1 : 0;
-    p.dbg_ego_per = c.debug_ego_per; p.dbg_ego_pad = c.debug_ego_pad; p.dbg_render_shape = c.debug_render_shape;
-    p.dbg_ego_miss_blocks = debug_env().ego_miss_blocks;
     p.n_tasks = c.n_tasks;
     p.group2d = c.n_tasks > 0 && c.tasks[0] >= XWB_TASK2D_TARGET;
     p.curriculum = curriculum ? c.curriculum : 0.0; p.cur_level = s->d_cur_level; p.cur_counter = s->d_cur_counter; p.cur_usage = s->d_cur_usage;
@@ -542,21 +533,9 @@ int xwb_create(const xwb_config *cfg, xwb_sim **out) {
     if (cfg->device < 0 || cfg->device >= ndev) return fail(XWB_ERR_ARG, "bad device ordinal");
     DeviceGuard _device_guard(cfg->device);           // the caller's current device is restored on return
     if (cfg->debug_flags & ~63) return fail(XWB_ERR_ARG, "unknown debug_flags bit");
-    if ((cfg->debug_ego_per != 0 && cfg->debug_ego_per != 2 && cfg->debug_ego_per != 4 && cfg->debug_ego_per != 8) || cfg->debug_ego_pad < 0 ||
-        cfg->debug_ego_pad > 65536 || cfg->debug_render_shape < 0 || cfg->debug_render_shape > 2)
-        return fail(XWB_ERR_ARG, "debug_ego_per must be 0 | 2 | 4 | 8, debug_ego_pad 0 .. 65536, debug_render_shape 0 .. 2");
     xwb_sim *s = new xwb_sim();
     s->cfg = *cfg;
-    {   // the process-wide override (XWB_DEBUG), see xwb.h
-        const DebugEnv &d = debug_env();
-        s->cfg.debug_flags |= d.flags;
-        // (the same range checks as the configuration's own fields: an entry outside them is ignored, with a warning)
-        if (d.ego_per == 2 || d.ego_per == 4 || d.ego_per == 8) s->cfg.debug_ego_per = d.ego_per;
-        else if (d.ego_per) fprintf(stderr, "libxwb: XWB_DEBUG: ego_per=%d ignored (2 | 4 | 8)\n", d.ego_per);
-        if (d.ego_pad > 0 && d.ego_pad <= 65536) s->cfg.debug_ego_pad = d.ego_pad;
-        else if (d.ego_pad) fprintf(stderr, "libxwb: XWB_DEBUG: ego_pad=%d ignored (0 .. 65535)\n", d.ego_pad - 1);
-        if (d.render_shape) s->cfg.debug_render_shape = d.render_shape;
-    }
+    s->cfg.debug_flags |= debug_env_flags();          // the process-wide override (XWB_DEBUG), see xwb.h
     s->device = cfg->device;
     s->n = cfg->num_envs;
     const int n = s->n;

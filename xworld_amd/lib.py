@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(HERE, "libxwb.so")
 if os.environ.get("XWB_LIB_AB"):                 # lab: another build of the same ABI, for A/B runs on ONE box (box-to-box spread is larger than most effects)
     LIB_PATH = os.path.abspath(os.environ["XWB_LIB_AB"])
 
-XWB_ABI_VERSION = 5
+XWB_ABI_VERSION = 6
 XWB_SIMPLE_GAME, XWB_SIMPLE_RACE, XWB_XWORLD2D = 0, 1, 2
 XWB_MAP_NAV, XWB_MAP_WALLS = 0, 1
 XWB_TASKMODE_LANG_ACQ, XWB_TASKMODE_ONE_CHANNEL = 0, 1
@@ -45,7 +45,7 @@ class XwbConfig(C.Structure):
         ("task_groups_exclusive", C.c_int32),
         ("task_group_weight", C.c_double), ("task_group_weight2", C.c_double),
         ("queue_sync", C.c_int32),
-        ("debug_flags", C.c_int32), ("debug_ego_per", C.c_int32), ("debug_ego_pad", C.c_int32), ("debug_render_shape", C.c_int32),
+        ("debug_flags", C.c_int32),
     ]
 
 
