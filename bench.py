@@ -2,6 +2,7 @@
 """bench.py -- env-steps/sec of the batched XWorld simulator on N MI355X (one process per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload xworld7|xworld8|xworld11|xworld7_ego3|...|simple_game|simple_race]
+                    [--full]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -16,14 +17,18 @@ Timing: W untimed warm-up steps, the same loop spun by wall time (--spin-seconds
 row agree within 1 %, then EXACTLY K steps between two barrier + synchronize fences, max over ranks, R times over (--repeats):
 `ms_per_step` / `value` are the MEDIAN region, the spread is reported (`regions`).
 
-Parity gate: every step of the run writes (reward, game_over) of every env into a device-side record
+A plain run does what the headline needs: set-up, warm-up, the timed regions, --dump-outputs, the line.  `--full` adds
+everything else below: the frame and parity gates, the event-timed regions and the write ceiling behind `roofline`, the
+secondary loops and workloads, the N > 1 screens gathers and C5 block, and `cpu_baseline`.
+
+Parity gate (--full): every step of the run writes (reward, game_over) of every env into a device-side record
 (xwb_bind_results_ring, no extra launches); after the timed regions the record of a slab of envs is compared, bit for bit, with
 the CPU oracle's rollout of the same envs from reset; a frame gate checks the first steps' frames.  The oracle is test
 infrastructure: bench_lib/parity.py is its only user here, outside every timed region.
 
-N = 1 also times, behind the main measurement, `step_autoreset`, `classic_path` and `secondary` (egocentric mode, SimpleGame,
+N = 1, --full also times, behind the main measurement, `step_autoreset`, `classic_path` and `secondary` (egocentric mode, SimpleGame,
 SimpleRace).  N > 1: the env batch is sharded by global env id (weak scaling); `value` = screens device-resident, one RCCL
-all-gather of (reward, game_over) per step; `screens_gather` / `c5` = secondary blocks, each under a watchdog phase
+all-gather of (reward, game_over) per step; `screens_gather` / `c5` (--full) = secondary blocks, each under a watchdog phase
 (bench_lib/watchdog.py).  `--dry-run` prints the planned phases and their budgets without touching a GPU.
 
 `--dump-outputs DIR` (N = 1) writes what the loop hands its caller after its last step (bench_lib/dump.py), so that two builds
@@ -64,6 +69,9 @@ def parse_args():
     ap.add_argument("--seed", type=lambda v: int(v, 0), default=0xC0FFEE, help="env RNG seed (xwb-rng-v1 key word 0)")
     ap.add_argument("--workload", default="xworld7", choices=list(WORKLOADS))
     ap.add_argument("--envs-per-gpu", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and measurements beyond the headline: frame and parity gates, roofline, step_autoreset, "
+                         "classic_path, secondary workloads, screens gathers, C5 at N = 8, cpu_baseline")
     ap.add_argument("--no-screens-gather", action="store_true", help="N > 1: skip the screens-gather-inclusive regions")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -80,7 +88,7 @@ def parse_args():
     ap.add_argument("--gather", default="both", choices=["screens", "grids", "grids_nodraw", "both"],
                     help="N > 1, full observation: what crosses the links per step -- every shard's pixels (screens), or its cell "
                          "codes with the root drawing all frames (grids), or one set of regions each (both)")
-    ap.add_argument("--c5", action="store_true", help="N > 1: add the BASELINE C5 block (xworld11); on by itself at N = 8")
+    ap.add_argument("--c5", action="store_true", help="N > 1: add the BASELINE C5 block (xworld11); on by itself at N = 8 with --full")
     ap.add_argument("--force-exchange", action="store_true",
                     help="N = 1: initialise torch.distributed (world size 1) and issue the N > 1 run's exchanges all the same")
     ap.add_argument("--results-wait", action="store_true",
@@ -95,6 +103,18 @@ def parse_args():
     return ap.parse_args()
 
 
+def phases(args, world):
+    """the phases of this invocation (bench_lib/plan.py plans a --full run): without --full the main measurement alone, with
+    C5 when --c5 asks for it by name"""
+    ph = plan(args, world)
+    if args.full:
+        return ph
+    keep = ("main", "teardown") + (("c5",) if args.c5 else ())
+    ph = [p for p in ph if p["phase"] in keep]
+    ph[0] = dict(ph[0], what="set-up, warm-up, spin, settle, %d timed regions of %d steps" % (args.repeats, args.steps))
+    return ph
+
+
 def main():
     args = parse_args()
     # (a dry run without a launcher plans for --gpus ranks; a real run is as wide as its launcher made it)
@@ -103,7 +123,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.dry_run:
         if rank == 0:
-            print(json.dumps({"dry_run": True, "n_gpus": world, "workload": args.workload, "phases": plan(args, world)}))
+            print(json.dumps({"dry_run": True, "n_gpus": world, "workload": args.workload, "phases": phases(args, world)}))
         return
     if args.dump_outputs and world > 1:
         sys.exit("bench.py: --dump-outputs runs in one process (N = 1)")
@@ -116,7 +136,7 @@ def main():
     guarded = world > 1 or forced
     PT = args.phase_timeout if guarded else None
     watchdog.watch_start(rank)
-    WATCH["pending"] = [p["phase"] for p in plan(args, world)]
+    WATCH["pending"] = [p["phase"] for p in phases(args, world)]
     watchdog.arm("main (set-up, frame gate, warm-up)", 3 * PT if PT else None)
     n_local = args.envs_per_gpu or WORKLOADS[args.workload][2]
     sim = make_sim(args.workload, n_local, local_rank, rank * n_local, args.seed)
@@ -133,7 +153,7 @@ def main():
         results = sharding.LibResultGather(sim, lib_comm_main, counts, rank)
     else:
         results = sharding.ResultGather(counts, rank, dev, force_collective=forced) if guarded else None
-    with_screens = guarded and not args.no_screens_gather
+    with_screens = guarded and args.full and not args.no_screens_gather
     L = Loop(args, sim, results, world, forced, dev, fused)
 
     # ---- plan the run: the record ring must exist before the first step; its length needs the step count, which needs the spin
@@ -142,7 +162,11 @@ def main():
     sim.bind_results_ring(L.rec)
     frames = None
     if not args.no_parity and fused == 1 and not (is_xworld and sim.obs_is_float):      # (float32 frames: the oracle renders uint8)
-        frames = frame_gate(args.workload, sim, L.one_step, L.fence, min(args.frame_envs, n_local), args.frame_steps, args.seed, rank)
+        if args.full:
+            frames = frame_gate(args.workload, sim, L.one_step, L.fence, min(args.frame_envs, n_local), args.frame_steps, args.seed, rank)
+        else:                                            # the gate's steps unchecked: the warm-up starts where a --full run's does
+            for _ in range(args.frame_steps):
+                L.one_step()
     for _ in range(3):
         L.one_step()
     L.fence()
@@ -158,7 +182,7 @@ def main():
     sim.bind_results_ring(L.rec)                         # (bind resets the library's slot counter: restart ours with it)
     probe_calls, L.calls = L.calls, 0
     # the write-ceiling anchor's buffer: allocated before the warm-up (nothing is allocated between the spin and the last region)
-    ceiling_buf = torch.empty(int(n_local * sim.obs_bytes_per_env), dtype=torch.uint8, device=dev)
+    ceiling_buf = torch.empty(int(n_local * sim.obs_bytes_per_env), dtype=torch.uint8, device=dev) if args.full else None
     for _ in range(W):
         L.one_step()
     # the last state reached after a number of steps the arguments fix: the spin and the settle regions below follow the wall clock
@@ -186,20 +210,22 @@ def main():
     regions = [L.timed_region() for _ in range(R)]
     dt_med = statistics.median(regions)
     host_us_per_step = statistics.median(L.host_issue) / args.steps * 1e6
-    # ---- R more regions with hipEvents around every launch of the dominant kernel (on its launch stream, recorded inside libxwb) ----
-    sim.profile_begin()
-    ev_regions = [L.timed_region() for _ in range(R)]
-    kern_us, kern_n = sim.profile_end("render" if is_xworld else "step")
-    kernels_us = {}
-    for kname in (("step", "render", "reset", "list") if is_xworld else ("step", "reset")):
-        us, nl = sim.profile_end(kname)                  # (each on the stream it runs on; the map generator runs BESIDE the render)
-        if nl:
-            kernels_us[kname] = {"avg_us": us, "launches": nl}
-    sim.profile_stop()
+    if args.full:
+        # ---- R more regions with hipEvents around every launch of the dominant kernel (on its launch stream, recorded inside libxwb) ----
+        sim.profile_begin()
+        ev_regions = [L.timed_region() for _ in range(R)]
+        kern_us, kern_n = sim.profile_end("render" if is_xworld else "step")
+        kernels_us = {}
+        for kname in (("step", "render", "reset", "list") if is_xworld else ("step", "reset")):
+            us, nl = sim.profile_end(kname)              # (each on the stream it runs on; the map generator runs BESIDE the render)
+            if nl:
+                kernels_us[kname] = {"avg_us": us, "launches": nl}
+        sim.profile_stop()
     path_default = sim.step_path()
-    ceiling = write_ceiling(ceiling_buf)                 # the run's own bandwidth anchor, behind everything the headline is read from
-    for _ in range(K):                                   # and the loop itself warm again before the secondary measurements
-        L.one_step()
+    if args.full:
+        ceiling = write_ceiling(ceiling_buf)             # the run's own bandwidth anchor, behind everything the headline is read from
+        for _ in range(K):                               # and the loop itself warm again before the secondary measurements
+            L.one_step()
     watchdog.disarm()
     ranks_seen = {}
     if guarded:                                          # N ranks on N devices, in the record itself
@@ -210,11 +236,21 @@ def main():
         ranks_seen = {"ranks": everyone, "ranks_seen": len({r["rank"] for r in everyone}),
                       "devices_seen": len({r["uuid"] or r["index"] for r in everyone})}
 
-    def core_line():
-        total_envs = n_local * world
+    def roofline():
         achieved = n_local * per_launch * fused / (kern_us * 1e-6) / 1e9 if kern_us > 0 else 0.0
         traffic, traffic_info = (measured_traffic(args.workload) if n_local == WORKLOADS[args.workload][2]
                                  else (None, {"traffic_source": None}))
+        step_loop = n_local * world * per_step * args.steps / dt_med / 1e9
+        return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "traffic": traffic, "kernel": dominant_kernel_name(kernel_name, path_default["path"]),
+                "write_ceiling_GBps": ceiling["memset"]["GBps"], "write_ceiling": ceiling,
+                "frac_of_write_ceiling": achieved / ceiling["memset"]["GBps"] if ceiling["memset"]["GBps"] else None,
+                "kernels_us": kernels_us, "kernel_avg_us": kern_us, "kernel_launches": kern_n,
+                "algorithmic_bytes_per_launch": n_local * per_launch * fused, "algorithmic_bytes_per_env_step": per_step,
+                "step_loop_GBps": step_loop, "step_loop_frac": step_loop / HBM_PEAK_GBS / world, **traffic_info}
+
+    def core_line():
+        total_envs = n_local * world
         if not guarded:
             exchange = "none"
         else:
@@ -224,8 +260,7 @@ def main():
                 "the step's stream waits for it one step late" if args.results_wait else "released: no reader on the step's stream", who)
         loop_name = (("step_n(%d): %d steps per launch, auto-reset" % (fused, fused)) if fused > 1 else
                      ("step_autoreset" if args.autoreset else "step + reset_done"))
-        step_loop = total_envs * per_step * args.steps / dt_med / 1e9
-        return {
+        core = {
             "metric": "env-steps/sec (batched random policy)", "value": total_envs * args.steps / dt_med, "unit": "env-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt_med / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -241,26 +276,22 @@ def main():
                         "untimed_before": {"warmup_steps": args.warmup, "spin_steps": spun * fused, "spin_seconds_target": args.spin_seconds,
                                            "probe_steps": probe_calls * fused, "settle_regions": len(settle)}},
             "path": path_default,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "kernel": dominant_kernel_name(kernel_name, path_default["path"]),
-                         "write_ceiling_GBps": ceiling["memset"]["GBps"], "write_ceiling": ceiling,
-                         "frac_of_write_ceiling": achieved / ceiling["memset"]["GBps"] if ceiling["memset"]["GBps"] else None,
-                         "kernels_us": kernels_us, "kernel_avg_us": kern_us, "kernel_launches": kern_n,
-                         "algorithmic_bytes_per_launch": n_local * per_launch * fused, "algorithmic_bytes_per_env_step": per_step,
-                         "step_loop_GBps": step_loop, "step_loop_frac": step_loop / HBM_PEAK_GBS / world, **traffic_info},
-            "timed_with_events_ms_per_step": statistics.median(ev_regions) / args.steps * 1e3,
-            "host_us_per_step": host_us_per_step,
-            "rccl": dict(sharding.backend_info(), **ranks_seen,
-                         **({"results_exchange": "libxwb.so" if lib_comm_main is not None else "torch.distributed",
-                             "results_exchange_note": lib_note} if guarded else {})),
         }
+        if args.full:
+            core["roofline"] = roofline()
+            core["timed_with_events_ms_per_step"] = statistics.median(ev_regions) / args.steps * 1e3
+        core["host_us_per_step"] = host_us_per_step
+        core["rccl"] = dict(sharding.backend_info(), **ranks_seen,
+                            **({"results_exchange": "libxwb.so" if lib_comm_main is not None else "torch.distributed",
+                                "results_exchange_note": lib_note} if guarded else {}))
+        return core
 
     line = core_line() if rank == 0 else None
     WATCH["line"] = line
     watchdog.done("main")
 
     # ---- xwb_step_autoreset: a finished env's observation is the first frame of its next episode -- NOT the loop `value` is quoted on
-    if fused == 1 and not args.autoreset:
+    if args.full and fused == 1 and not args.autoreset:
         L.autoreset = True
         with phase("step_autoreset", PT):
             for _ in range(K):
@@ -272,7 +303,8 @@ def main():
         if rank == 0:
             line["step_autoreset"] = ar
     watchdog.done("step_autoreset")
-    if is_xworld and world == 1 and fused == 1 and not args.autoreset and path_default["path"] in ("lazy", "lazy_fused"):
+    if (args.full and is_xworld and world == 1 and fused == 1 and not args.autoreset
+            and path_default["path"] in ("lazy", "lazy_fused")):
         line["classic_path"] = secondary.classic_line(args.workload, n_local, local_rank, args.seed, K, W, args.steps,
                                                       args.spin_seconds, per_step)
     watchdog.done("classic_path")
@@ -323,7 +355,7 @@ def main():
         if world > 1:
             line["multi_gpu_note"] = ("value / screens_gather / c5 are this run's measurements; DESIGN.md carries no 8-GPU number of "
                                       "its own until a SCALE record exists")
-        if not args.no_parity:                           # the checker leg: nothing above this line touched the oracle
+        if args.full and not args.no_parity:             # the checker leg: nothing above this line touched the oracle
             line["parity"] = parity_gate(args.workload, L.rec, L.calls, slots, fused, 0, args.seed, min(args.parity_envs, n_local), probe_calls)
             if frames is not None:
                 line["parity"]["frames"] = frames
@@ -341,7 +373,7 @@ def main():
                                     "arrays": dump.write_outputs(sim, L.rec[(L.calls - 1) % L.rec.shape[0]], args.dump_outputs)}
         if forced:
             line["forced_exchange"] = "world size 1: the N > 1 run's collectives were issued all the same (they move nothing between GPUs)"
-        if not args.no_cpu_baseline and world == 1:      # rank 0, N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0, N = 1 only
             line["cpu_baseline"] = cpu_baseline(args.workload, args.seed)
         print(json.dumps(line))
         sys.stdout.flush()

@@ -7,9 +7,12 @@ fences) can resolve: settled lines read +1.4, -3.2, +1.6, +0.1, +1.5 % with the 
 A 1 % gate on this command would fail the suite on four boxes out of five; the gate is 2.5 % on either of TWO lines (round 5:
 three), and every retry is printed.  The line also carries the default loop's step path (one launch per step from the second
 step on), its loop at >= 0.745 of the HBM roofline on these short regions (measured 0.753-0.79 box to box; 200-step regions
-0.786-0.816), and the `secondary` workloads -- egocentric mode, SimpleGame, SimpleRace -- each with a parity slab."""
+0.786-0.816), and the `secondary` workloads -- egocentric mode, SimpleGame, SimpleRace -- each with a parity slab: those are
+--full's, so that line is the driver's arguments with --full.  Without it the line carries the headline and nothing that takes
+runs of its own."""
 import json
 import os
+import statistics
 import subprocess
 import sys
 
@@ -29,10 +32,10 @@ def _line(extra):
 
 @pytest.mark.gpu
 def test_driver_args_line_is_settled_and_complete():
-    d = _line([])
+    d = _line(["--full"])
     if abs(d["regions"]["trend"]) >= 0.025:
         print("RETRY: trend %+.4f, regions %s" % (d["regions"]["trend"], d["regions"]["ms_per_step_all"]))
-        d2 = _line(["--no-cpu-baseline"])
+        d2 = _line(["--full", "--no-cpu-baseline"])
         print("second line: trend %+.4f, regions %s" % (d2["regions"]["trend"], d2["regions"]["ms_per_step_all"]))
         assert abs(d2["regions"]["trend"]) < 0.025, (d["regions"], d2["regions"])
     print("trend", d["regions"]["trend"], "ms_per_step", d["ms_per_step"], "all", d["regions"]["ms_per_step_all"])
@@ -56,6 +59,24 @@ def test_driver_args_line_is_settled_and_complete():
     assert sec["xworld7_ego3"]["path"]["path"] == "ego_span" and sec["xworld7_ego3"]["value"] > 1.0e8
     assert sec["simple_game"]["one_launch"]["value"] > sec["simple_game"]["value"] > 2.0e9
     assert sec["simple_race"]["one_launch"]["value"] > sec["simple_race"]["value"] > 2.0e9
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline():
+    """the driver's arguments without --full: the headline fields as a --full line has them, none of the checks and
+    measurements that run behind the main loop"""
+    d = _line([])
+    assert d["metric"] == "env-steps/sec (batched random policy)" and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u8" and d["config"]["workload"] == "xworld7" and d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5
+    reg = d["regions"]
+    assert reg["repetitions"] == 9 and d["ms_per_step"] == statistics.median(reg["ms_per_step_all"])
+    assert abs(d["value"] - 32768 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    # the steps before the warm-up are a --full run's (the frame gate's, unchecked): the timed loop starts from the same state
+    assert reg["untimed_before"]["probe_steps"] == 24 + 13
+    assert d["path"]["path"] == "lazy_fused" and d["host_us_per_step"] > 0
+    for moved in ("roofline", "timed_with_events_ms_per_step", "step_autoreset", "classic_path", "secondary", "parity", "cpu_baseline"):
+        assert moved not in d, moved
+    assert d["phase_seconds"] == {}
 
 
 @pytest.mark.gpu

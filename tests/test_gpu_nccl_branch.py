@@ -104,7 +104,7 @@ def test_bench_forced_exchange_reports_rccl(exchange):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
            "--repeats", "3", "--spin-seconds", "0.02", "--envs-per-gpu", "2048", "--backend", "nccl", "--force-exchange",
-           "--exchange", exchange, "--no-cpu-baseline"]
+           "--exchange", exchange, "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

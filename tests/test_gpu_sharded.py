@@ -120,7 +120,7 @@ def test_bench_two_ranks_on_one_gpu(workload, extra):
     device-resident value, the screens-gather figures, what the exchange ran on, and a clean parity gate."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--repeats", "3", "--spin-seconds", "0.02", "--envs-per-gpu", "1024", "--backend", "gloo", "--workload", workload] + extra
+           "--repeats", "3", "--spin-seconds", "0.02", "--envs-per-gpu", "1024", "--backend", "gloo", "--workload", workload, "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

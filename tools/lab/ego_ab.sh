@@ -13,7 +13,7 @@ for B in "${BUILDS[@]}"; do
   di=0
   for D in "${DEBUGS[@]}"; do
     for WL in $WLS; do
-      XWB_DEBUG="$D" timeout 600 python bench.py --workload $WL --steps 100 --warmup 20 --repeats 5 --no-cpu-baseline 2>$OUT/bench_${WL}_${bi}_$di.err | grep '^{"metric"' | tail -1 > $OUT/bench_${WL}_${bi}_$di.json
+      XWB_DEBUG="$D" timeout 600 python bench.py --workload $WL --steps 100 --warmup 20 --repeats 5 --full --no-cpu-baseline 2>$OUT/bench_${WL}_${bi}_$di.err | grep '^{"metric"' | tail -1 > $OUT/bench_${WL}_${bi}_$di.json
       python - "$OUT/bench_${WL}_${bi}_$di.json" "$WL" "$B" "$D" <<'PY'
 import json, sys
 try:

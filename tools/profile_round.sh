@@ -13,10 +13,10 @@ for W in "$@"; do
   cp gpurun_out/prof_$W/traffic.json $OUT/traffic_$W.json 2>/dev/null
   mkdir -p profiles/$TAG && cp gpurun_out/prof_$W/traffic.json profiles/$TAG/traffic_$W.json 2>/dev/null
   rm -rf gpurun_out/prof_$W                                # (raw traces: ~25 MB per workload; gpurun brings back at most 64 MiB)
-  python bench.py --workload $W > $OUT/bench_$W.json 2> $OUT/bench_$W.err || true
+  python bench.py --workload $W --full > $OUT/bench_$W.json 2> $OUT/bench_$W.err || true
   tail -c 300 $OUT/bench_$W.json | head -c 300; echo
 done
-python bench.py --workload xworld7 --autoreset --no-cpu-baseline > $OUT/bench_xworld7_autoreset.json 2>/dev/null || true
+python bench.py --workload xworld7 --autoreset --full --no-cpu-baseline > $OUT/bench_xworld7_autoreset.json 2>/dev/null || true
 # SQ / TA / TCP counters of the egocentric span path per radius (tools/pmc_ego_span.sh)
 for RM in "3 7" "5 8" "7 7"; do
   set -- $RM
@@ -24,5 +24,5 @@ for RM in "3 7" "5 8" "7 7"; do
   { echo "== commit ${GIT_HEAD:-unknown} (tools/pmc_ego_span.sh $1 $2) =="; cat gpurun_out/pmc_ego_span_r$1/summary.txt; } > $OUT/ego_r$1_span_counters.txt
 done
 python tools/ego_sweep.py > $OUT/ego_sweep.txt 2>&1 || true
-python bench.py --steps 20 --warmup 5 > $OUT/bench_xworld7_driver_args.json 2>/dev/null || true
+python bench.py --steps 20 --warmup 5 --full > $OUT/bench_xworld7_driver_args.json 2>/dev/null || true
 ls -la $OUT
