@@ -2,7 +2,11 @@
 """Random-policy rollouts, the shape of the reference's python/examples/test_*.py -- once through the
 py_simulator-compatible object (one env, Python dicts), once through the batch API (device tensors).
 
-    python examples/rollout.py [simple_game|simple_race|xworld|xworld_ego]
+    python examples/rollout.py [simple_game|simple_race|xworld|xworld_ego] [--frames DIR [--frame-envs K]]
+
+--frames DIR (xworld, xworld_ego): the batch rollout also writes the first K envs' views of every step (render_view: the
+64-pixel-per-cell image behind the observation) as DIR/<game>_env<e>_step<t>.png -- what take_actions(..., show_screen=True)
+put into a window.  Views are B,G,R like the reference's cv::Mat; they are flipped to R,G,B for the PNG here.
 """
 import os
 import random
@@ -41,16 +45,26 @@ def single_env(name, opts, steps=200):
                                                                        game.get_screen_out_dimensions()))
 
 
-def batch(name, opts, num_envs=4096, steps=200):
+def batch(name, opts, num_envs=4096, steps=200, frames=None, frame_envs=4, tag=""):
     import torch
     sim = BatchedSimulator(name, opts, num_envs=num_envs)
+    view = None
+    if frames and name == "xworld":
+        from PIL import Image
+        os.makedirs(frames, exist_ok=True)
+        k = min(frame_envs, num_envs)
+        view = torch.empty((k,) + sim.view_dims, dtype=torch.uint8, device="cuda")     # reused by every step
     total = torch.zeros(num_envs, device="cuda")
     finished = 0
-    for _ in range(steps):
+    for t in range(steps):
         actions = torch.randint(0, sim.num_actions, (num_envs,), dtype=torch.int32, device="cuda")
         sim.step(actions)                            # obs / reward / game_over_codes are device tensors (views)
         total += sim.reward
         finished += int((sim.game_over_codes != 0).sum())
+        if view is not None:                         # (before the reset: a finished env still shows its last state)
+            rgb = sim.render_view(k, out=view).flip(-1).cpu().numpy()                  # B,G,R -> R,G,B
+            for e in range(k):
+                Image.fromarray(rgb[e]).save(os.path.join(frames, "%s_env%d_step%04d.png" % (tag, e, t)))
         sim.reset_done()                             # `if game_over: reset_game()` for the whole batch
     print("%s: %d envs, %d steps, %d episodes finished, mean reward %.3f, obs %s %s" % (
         name, num_envs, steps, finished, float(total.mean()), tuple(sim.obs.shape), sim.obs.dtype))
@@ -58,8 +72,15 @@ def batch(name, opts, num_envs=4096, steps=200):
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or list(OPTS)
-    for w in which:
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("games", nargs="*", metavar="|".join(OPTS))
+    ap.add_argument("--frames", metavar="DIR", help="write the first K envs' views of every step as PNGs (xworld, xworld_ego)")
+    ap.add_argument("--frame-envs", type=int, default=4, metavar="K")
+    args = ap.parse_args()
+    for w in args.games or list(OPTS):
+        if w not in OPTS:
+            ap.error("unknown game " + w)
         name, opts = OPTS[w]
         single_env(name, dict(opts))
-        batch(name, dict(opts))
+        batch(name, dict(opts), frames=args.frames, frame_envs=args.frame_envs, tag=w)

@@ -518,6 +518,36 @@ int xwb_xw_set_draw(xwb_sim *sim, int32_t on);
 int xwb_xw_render_grids(xwb_sim *sim, const uint16_t *grids_dev, const uint8_t *flags_dev, int32_t n_envs, void *obs_dev,
                         void *stream);
 
+/* ---- views at native resolution: the image behind a frame ----
+ * xwb_xw_render_view draws, for chosen envs of an XWorld2D batch, the view the env's NEWEST observation frame was made from,
+ * before XWorldSimulator's resizes: 64 pixels per cell, uint8, interleaved B,G,R, rows top to bottom (the layout of the
+ * reference's cv::Mat) -- always colour and always uint8, whatever color / obs_format / context the batch was created with.
+ *   full observation   [64 max_dim][64 max_dim][3] = XMap::to_image(agent, false, 0): a white canvas with every cell's item
+ *                      image copied in (xmap.cpp:125-146), what get_screen_rgb sees
+ *   egocentric         [64 r][64 r][3] = XMap::to_image(agent, false, r): the window in front of the agent, wall shadows
+ *                      black (unless no_wall_shadow), turned by 90 + yaw degrees (xmap.cpp:148-200); every odd r the batch accepts
+ * xwb_xw_view_dims reports h, w, c = 64 k, 64 k, 3.  Pushing a view through the resize(s) gives the env's current frame byte
+ * for byte; in particular an env that the last xwb_step finished and that has not been reset yet shows its terminal state, as
+ * its frame does (full observation: the selection of xwb_xw_pack_grids; egocentric: the library still holds heading, goal
+ * images and map of such an env on every step path -- lazy, fused, classic, autoreset -- until the reset runs, so it is drawn,
+ * never zero-filled), and neither the look-ahead snapshots of the default loop nor pre-generated episodes show up in a view.
+ * With xwb_xw_set_draw(sim, 0) the observation buffer is stale by design; a view then shows what xwb_xw_pack_grids reports.
+ * envs_dev = NULL: envs 0 .. n - 1; else n env indices in DEVICE memory (int32, repeats allowed).  out_dev: [n][h][w][3],
+ * 16-byte aligned, out_bytes its size.  XWB_ERR_ARG, and nothing is launched: out_bytes smaller than n views, n < 0,
+ * n > num_envs with a NULL list, a game other than XWorld2D.  n = 0 does nothing.  An index outside [0, num_envs) read from
+ * the device list cannot be refused by the host: that slot is filled with zeros and nothing else happens (no error is counted).
+ * A poisoned batch: XWB_ERR_STATE.
+ * One kernel launch on `stream`, behind the verbs queued there before it; no allocation, no copy, no host synchronisation.  It
+ * reads; it changes no state: which path the next xwb_step takes (xwb_step_path), the snapshot and pre-generation flags and
+ * every result of a rollout are the same with and without views in between.  (Egocentric batches: one event orders the
+ * internal queue's LATER work -- an xwb_reset_done's map generator -- behind the view kernel.)
+ * Cost: views are large -- 786 432 bytes per env at 8 x 8, 307 200 at r = 5; 32 768 envs at 8 x 8 would be 25.8 GB -- the call
+ * draws what it is asked for into the caller's buffer.  Every full-observation XWorld2D batch keeps a 3-byte-per-pixel copy
+ * of the item images on the device for it ((n_icons + 1) * 12 288 bytes, 4-6 MB for the shipped palettes), uploaded by
+ * xwb_create; egocentric batches read the atlas and goal images their frame render already holds. */
+int xwb_xw_view_dims(const xwb_sim *sim, size_t *h, size_t *w, size_t *c);
+int xwb_xw_render_view(xwb_sim *sim, const int32_t *envs_dev, int32_t n, void *out_dev, size_t out_bytes, void *stream);
+
 /* (test and measurement hooks -- xwb_debug_stall_handoff, xwb_profile_begin / _end / _stop -- are not part of this boundary:
  * include/xwb_testing.h, version node XWB_TESTING of csrc/libxwb.map) */
 

@@ -407,6 +407,61 @@ class BatchedSimulator:
         lib.check(self.L.xwb_xw_render_grids(self.h, C.c_void_p(grids.data_ptr()), C.c_void_p(flags.data_ptr()) if flags is not None else None,
                                              n, C.c_void_p(out.data_ptr()), self._stream(stream)))
 
+    @property
+    def view_dims(self):
+        """xwb_xw_view_dims: (h, w, 3) of one env's native-resolution view -- 64 pixels per cell of the map (full observation) or of
+        the visible window (egocentric)."""
+        hh, ww, cc = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        lib.check(self.L.xwb_xw_view_dims(self.h, C.byref(hh), C.byref(ww), C.byref(cc)))
+        return (hh.value, ww.value, cc.value)
+
+    def render_view(self, envs=None, out=None, stream=None):
+        """xwb_xw_render_view: the views the newest frames of the chosen envs were made from, before the simulator's resizes --
+        uint8 CUDA tensor [k, h, w, 3], pixels interleaved B,G,R (flip the last axis for an R,G,B image), always colour.
+        envs: None (every env), an int k (the first k), a Python sequence or CPU tensor of env indices (checked here: IndexError
+        for one outside [0, num_envs); then copied to the device), or an int32 CUDA tensor (used as it is, no host round trip: an
+        index outside the batch gives a zero-filled slot).  out: a contiguous uint8 tensor [k, h, w, 3] on the batch's device to
+        draw into; without it k * h * w * 3 bytes are allocated per call (786 432 per env at 8 x 8).  Reads only: nothing
+        about the rollout changes."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        idx = host = None
+        if envs is None:
+            k = self.num_envs
+        elif isinstance(envs, int) and not isinstance(envs, bool):
+            k = envs
+            if k < 0 or k > self.num_envs:
+                raise IndexError("render_view: %d envs asked for, the batch has %d" % (k, self.num_envs))
+        elif isinstance(envs, torch.Tensor) and envs.is_cuda:
+            if envs.dtype != torch.int32 or envs.dim() != 1 or not envs.is_contiguous() or envs.device != dev:
+                raise ValueError("envs: a contiguous 1-d int32 tensor on %s" % dev)
+            idx, k = envs, int(envs.numel())
+        else:
+            host = torch.as_tensor(envs, dtype=torch.int64).reshape(-1)
+            if host.numel() and (int(host.min()) < 0 or int(host.max()) >= self.num_envs):
+                raise IndexError("render_view: env index out of range [0, %d)" % self.num_envs)
+            k = int(host.numel())
+        shape = (k,) + tuple(self._view_shape())
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+            if isinstance(stream, torch.cuda.Stream):          # the caching allocator hands it out for the current stream
+                out.record_stream(stream)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != shape \
+                or not out.is_contiguous():
+            raise ValueError("out: a contiguous uint8 tensor of shape %s on %s" % (shape, dev))
+        if k:
+            if host is not None:
+                idx = host.to(torch.int32).to(dev)
+            lib.check(self.L.xwb_xw_render_view(self.h, C.c_void_p(idx.data_ptr()) if idx is not None else None, k,
+                                                C.c_void_p(out.data_ptr()), out.numel(), self._stream(stream)))
+            self._view_idx = idx                               # (keeps a list copied from the host alive until the next call)
+        return out
+
+    def _view_shape(self):
+        if getattr(self, "_view_hwc", None) is None:
+            self._view_hwc = self.view_dims
+        return self._view_hwc
+
     def env_state(self, env=0, stream=None):
         st = lib.XwbEnvState()
         lib.check(self.L.xwb_get_env_state(self.h, int(env), self._stream(stream), C.byref(st)))

@@ -26,6 +26,7 @@
 // this kernel bit for bit with a CPU restatement of the same pipeline; pixel parity with the real library is unpinned.
 #include "xwb_common.h"
 #include "xw_device.h"
+#include "xw_ego_cells.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -50,15 +51,6 @@ __device__ unsigned long long g_ego_prof2[12];     // stage stamps of the whole-
 struct EgoTap { int16_t s0, s1, w0, w1; };        // cv::resize: source indices and 11-bit weights of one output index
 
 namespace {
-
-// What one cell of the view shows: a 64 x 64 image (block icon, this env's warped goal image, the agent icon turned for
-// its heading -- the three turned copies of every agent icon are appended to the atlas at create time) or one constant
-// pixel (mask = 0).  The table makes the per-pixel lookup branch-free: one 16-byte LDS read, an AND and an add.
-struct EgoCell {
-    const uint32_t *img;
-    int mask;                    // -1: index the image; 0: a constant pixel
-    int tab;                     // frame of the interior-pixel table that shows this cell's image, -1: none (a goal)
-};
 
 struct EgoCtx {
     const EgoCell *cells;        // LDS, r * r
@@ -295,15 +287,6 @@ __device__ __forceinline__ void ego_copy_interior(const EgoCell *s_cells, const 
     }
 }
 
-// What one view cell shows.  dir: heading; tab: -1 for goals (their images are per env)
-__device__ __forceinline__ EgoCell ego_icon_cell(const uint8_t *icon_type, const uint32_t *agent_rot, const uint32_t *atlas4,
-                                                 int icon, int dir) {
-    EgoCell c{atlas4 + (size_t)icon * 4096, -1, icon * 4 + dir};
-    // the agent: XItem::get_item_image turns its icon by 90 - yaw deg
-    if (icon_type[icon] == 2 && dir != 1) c.img = atlas4 + agent_rot[icon] + (size_t)(dir == 0 ? 0 : (dir == 2 ? 1 : 2)) * 4096;
-    return c;
-}
-
 __device__ __forceinline__ void ego_compose_taps(EgoTap (*s_row)[3], EgoTap (*s_col)[3], const EgoTap *tap_h1, const EgoTap *tap_v1,
                                                  const EgoTap *tap_h2, const EgoTap *tap_v2, int O, int tid, int bs) {
     for (int i = tid; i < O; i += bs) {
@@ -398,7 +381,6 @@ __global__ __launch_bounds__(BS, 4) void xw_render_ego_kernel(XwParams p, const 
         f.valid = (FAST && p.ego_cache_valid && tid < (int)p.ego_cache_words && tid < 64) ? p.ego_cache_valid[(size_t)f.e * p.ego_cache_words + tid] : 0u;
         return f;
     };
-    auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); };
     Fetch nxt{};
     if ((int)blockIdx.x < n_items) nxt = fetch(blockIdx.x);
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
@@ -430,54 +412,12 @@ __global__ __launch_bounds__(BS, 4) void xw_render_ego_kernel(XwParams p, const 
             auto is_block = [&](int x, int y) {
                 return (unsigned)x < (unsigned)D && (unsigned)y < (unsigned)D && s_type[y * D + x] == 1;
             };
-            // XMap::image_masking (xmap.cpp:273-362)
-            int major_x = 0, major_y = 0, minor_x = 0, minor_y = 0, scan_x0 = 0, scan_y0 = 0, xa = ax + r, ya = ay + r;
-            if (dir == 0) { xa += r / 2; major_y = 1; minor_x = 1; }
-            else if (dir == 3) { ya -= r / 2; major_x = 1; minor_y = -1; scan_y0 = r - 1; }
-            else if (dir == 2) { xa -= r / 2; major_y = 1; minor_x = -1; scan_x0 = r - 1; }
-            else { ya += r / 2; major_x = 1; minor_y = 1; }
-            const int x_st = xa - r / 2, y_st = ya - r / 2;
-            wave_sync();
-            if (tid < 2) {                                      // rays to either side of the agent
-                const int o = tid ? 1 : -1;
-                bool block = false;
-                int rx = ax, ry = ay;
-                for (int k = 1; k <= r / 2; ++k) {
-                    rx += o * major_x; ry += o * major_y;
-                    if (block) s_ray[r / 2 + o * k] = 0;
-                    if (is_block(rx, ry)) block = true;
-                }
-            }
-            wave_sync();
-            if (tid < r) {                                      // one scan line per lane
-                bool block = !s_ray[tid];
-                int cx = scan_x0 + tid * major_x, cy = scan_y0 + tid * major_y;
-                for (int j = 0; j < r; ++j) {
-                    s_shadow[cy * r + cx] = block ? 1 : 0;
-                    if (is_block(x_st - r + cx, y_st - r + cy)) block = true;
-                    cx = (cx + minor_x + r) % r;
-                    cy = (cy + minor_y + r) % r;
-                }
-            }
-            wave_sync();
+            const EgoWindow win = ego_image_masking(r, ax, ay, dir, tid, s_ray, s_shadow, is_block);
             const uint32_t *gimg = p.goal_img + (size_t)e * p.num_goals * 4096;
             for (int k = tid; k < r * r; k += 64) {             // what each view cell shows
-                const int gx = x_st - r + k % r, gy = y_st - r + k / r;
-                EgoCell c{black, 0, (p.n_icons + 1) * 4 + dir}; // outside the map, or in a wall's shadow
-                if ((unsigned)gx < (unsigned)D && (unsigned)gy < (unsigned)D && !(s_shadow[k] && !p.no_wall_shadow)) {
-                    const int code = s_code[gy * D + gx];
-                    if (code == 0) { c.img = white; c.tab = p.n_icons * 4 + dir; }
-                    else {
-                        c = ego_icon_cell(s_itype, s_rot, atlas4, code - 1, dir);
-                        if (s_type[gy * D + gx] == 0) {         // a goal: this env's warped copy
-                            int slot = 0;
-                            for (int i = 0; i < XW_MAX_GOALS; ++i) if (s_gc[i] == gy * D + gx) slot = i;
-                            c.img = gimg + slot * 4096;
-                            c.tab = -1;
-                            if (FAST) { const int j = atomicAdd(&s_ngoal, 1); s_goal_k[j] = (uint8_t)k; s_goal_slot[j] = (uint8_t)slot; }
-                        }
-                    }
-                }
+                int slot;
+                const EgoCell c = ego_window_cell(p, atlas4, s_itype, s_rot, s_code, s_type, s_shadow, s_gc, gimg, win, k, dir, &slot);
+                if (FAST && slot >= 0) { const int j = atomicAdd(&s_ngoal, 1); s_goal_k[j] = (uint8_t)k; s_goal_slot[j] = (uint8_t)slot; }
                 s_cells[k] = c;
             }
         }

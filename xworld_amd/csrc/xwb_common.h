@@ -371,6 +371,10 @@ hipError_t launch_xw_reset(const XwParams &p, int mode, hipStream_t s);
 hipError_t launch_xw_compact(const XwParams &p, int mode, hipStream_t s);
 // the batch's draw state (cell codes its current frames show + context-ring flags) for a renderer elsewhere; src: PACK_SRC_*
 hipError_t launch_xw_pack_grids(const XwParams &p, int src, uint16_t *out_grid, uint8_t *out_flag, hipStream_t s);
+// views at native resolution (kernels_xworld_view.hip): n slots of [64 k][64 k][3] bytes (k = max_dim, or visible_radius) into
+// `out`, slot i = env envs[i] (device memory; NULL: env i; an index outside the batch: zeros).  src: PACK_SRC_*, full observation;
+// view_atlas: xwb_sim::d_view_atlas (full observation; egocentric batches read atlas64 / goal_img)
+hipError_t launch_xw_view(const XwParams &p, int src, const int32_t *envs, int n, const void *view_atlas, void *out, hipStream_t s);
 // full observation: RENDER_ALL / RENDER_ALIVE / RENDER_ALL_TERM (LDS-resident atlas, persistent workgroups), RENDER_LIST (atlas
 // through L2); egocentric: launch_xw_render_ego (RENDER_ALL_TERM draws as RENDER_ALL there)
 hipError_t launch_xw_render(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);

@@ -317,6 +317,14 @@ int xw_setup(xwb_sim *s) {
         HIP_TRY(hipMemcpy(s->d_agent_rot, rot_off.data(), rot_off.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(xw_ego_tables(c.visible_radius, c.max_dim, s->out_h, &s->d_ego_taps, &s->xw.ego_fast, &s->ego_cell_edge, &s->xw.ego_span));
         s->allocs.push_back(s->d_ego_taps);
+        HIP_TRY(hipEventCreateWithFlags(&s->ev_view, hipEventDisableTiming | hipEventDisableSystemFence));
+    } else {
+        // xwb_xw_render_view gathers whole 16-byte pieces from the item images as the view stores them: 3 bytes per pixel
+        const size_t cell = 64 * 64 * 3;
+        std::vector<uint8_t> a3((size_t)(c.n_icons + 1) * cell, 255);
+        memcpy(a3.data() + cell, c.icons64, (size_t)c.n_icons * cell);
+        if ((rc = dev_alloc(s, &s->d_view_atlas, a3.size()))) return rc;
+        HIP_TRY(hipMemcpy(s->d_view_atlas, a3.data(), a3.size(), hipMemcpyHostToDevice));
     }
     if ((rc = dev_alloc(s, &s->d_icon_name, c.n_icons))) return rc;
     if ((rc = dev_alloc(s, &s->d_name_first, first.size()))) return rc;
@@ -650,6 +658,7 @@ int xwb_destroy(xwb_sim *s) {
     if (s->ev_term) (void)hipEventDestroy(s->ev_term);
     if (s->ev_cells) (void)hipEventDestroy(s->ev_cells);
     if (s->ev_results) (void)hipEventDestroy(s->ev_results);
+    if (s->ev_view) (void)hipEventDestroy(s->ev_view);
     for (KernelTimer *t : {&s->t_render, &s->t_step, &s->t_reset, &s->t_list})
         for (auto &ep : t->pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     delete s;

@@ -100,6 +100,7 @@ struct xwb_sim {
     uint32_t *h_poison = nullptr;          // pinned host word: a watchdog expired (XwParams::poison_host points at it)
     bool poisoned = false;
     hipEvent_t ev_step = nullptr, ev_reset = nullptr, ev_term = nullptr, ev_cells = nullptr;
+    hipEvent_t ev_view = nullptr;          // egocentric xwb_xw_render_view: the internal queue's later work follows the view kernel
     hipEvent_t ev_results = nullptr;       // xwb_gather_results_beside's hand-over when the last step did not run on epochs (made on first use)
     // common device buffers
     int32_t *d_actions_in = nullptr;       // staging for xwb_step_host
@@ -169,6 +170,7 @@ struct xwb_sim {
     double *d_goal_warp = nullptr;
     int16_t *d_icon_name = nullptr, *d_name_first = nullptr, *d_name_variants = nullptr;
     uint32_t *d_atlas = nullptr;
+    uint8_t *d_view_atlas = nullptr;       // full observation, xwb_xw_render_view: [n_icons + 1][64][64][3] B,G,R (entry 0: a white cell)
     std::vector<uint8_t> tile_table;   // host copy, n_icons x c x 12 x 12
     std::vector<int32_t> icon_type_h, icon_name_h, icon_colored_h;
     // xwb_set_names: the strings behind the name ids (the teacher's sentences are built from them)

@@ -830,6 +830,42 @@ int xwb_xw_render_grids(xwb_sim *s, const uint16_t *grids_dev, const uint8_t *fl
     return XWB_OK;
 }
 
+int xwb_xw_view_dims(const xwb_sim *s, size_t *h, size_t *w, size_t *c) {
+    if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
+    if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_ARG, "not an xworld batch");
+    const size_t edge = 64u * (size_t)(s->cfg.visible_radius ? s->cfg.visible_radius : s->cfg.max_dim);
+    if (h) *h = edge;
+    if (w) *w = edge;
+    if (c) *c = 3;
+    return XWB_OK;
+}
+
+int xwb_xw_render_view(xwb_sim *s, const int32_t *envs_dev, int32_t n, void *out_dev, size_t out_bytes, void *stream) {
+    if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
+    XWB_ON_DEVICE(s);
+    XWB_LIVE(s);
+    if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_ARG, "not an xworld batch");
+    if (n < 0) return fail(XWB_ERR_ARG, "n must be >= 0");
+    if (!envs_dev && n > s->n) return fail(XWB_ERR_ARG, "n exceeds num_envs (without an index list the views are those of envs 0 .. n - 1)");
+    if (n == 0) return XWB_OK;
+    size_t edge = 0;
+    XWB_TRY(xwb_xw_view_dims(s, &edge, nullptr, nullptr));
+    if (!out_dev || out_bytes / (edge * edge * 3) < (size_t)n) return fail(XWB_ERR_ARG, "the output buffer is smaller than n views");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 15u) return fail(XWB_ERR_ARG, "the output buffer must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(envs_dev) & 3u) return fail(XWB_ERR_ARG, "the index list must be 4-byte aligned");
+    hipStream_t st = as_stream(stream);
+    // Ordered on `st` like xwb_xw_pack_grids, and reading what it reads: the live state (or xwb_step's terminal snapshots), never
+    // the look-ahead snapshots or the pre-generated episodes, which are all the internal queue writes on the full-observation paths.
+    HIP_TRY(launch_xw_view(xw_params(s), s->frame_src, envs_dev, n, s->d_view_atlas, out_dev, st));
+    if (s->cfg.visible_radius) {
+        // a finished egocentric env awaiting its reset is drawn from the live state (heading, goal images): an xwb_reset_done
+        // queued after this call regenerates it on the internal queue, beside whatever still runs on `st` -- not beside this kernel
+        HIP_TRY(hipEventRecord(s->ev_view, st));
+        HIP_TRY(hipStreamWaitEvent(s->side, s->ev_view, 0));
+    }
+    return XWB_OK;
+}
+
 int xwb_profile_begin(xwb_sim *s) {
     if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
     s->profiling = true;
