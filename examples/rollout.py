@@ -45,7 +45,7 @@ def single_env(name, opts, steps=200):
                                                                        game.get_screen_out_dimensions()))
 
 
-def batch(name, opts, num_envs=4096, steps=200, frames=None, frame_envs=4, tag=""):
+def batch(name, opts, num_envs=4096, steps=200, frames=None, frame_envs=4, tag="", policy="random"):
     import torch
     sim = BatchedSimulator(name, opts, num_envs=num_envs)
     view = None
@@ -56,8 +56,16 @@ def batch(name, opts, num_envs=4096, steps=200, frames=None, frame_envs=4, tag="
         view = torch.empty((k,) + sim.view_dims, dtype=torch.uint8, device="cuda")     # reused by every step
     total = torch.zeros(num_envs, device="cuda")
     finished = 0
+    expert = policy == "expert" and name == "xworld"
+    started = no_path = 0                            # expert: episodes begun, and those that began without any winning path
+    fresh = torch.ones(num_envs, dtype=torch.bool, device="cuda")
     for t in range(steps):
-        actions = torch.randint(0, sim.num_actions, (num_envs,), dtype=torch.int32, device="cuda")
+        if expert:                                   # the shortest path to the task's goal, computed on the device
+            actions, dist = sim.expert()
+            started += int(fresh.sum())
+            no_path += int((fresh & (dist < 0)).sum())
+        else:
+            actions = torch.randint(0, sim.num_actions, (num_envs,), dtype=torch.int32, device="cuda")
         sim.step(actions)                            # obs / reward / game_over_codes are device tensors (views)
         total += sim.reward
         finished += int((sim.game_over_codes != 0).sum())
@@ -65,9 +73,14 @@ def batch(name, opts, num_envs=4096, steps=200, frames=None, frame_envs=4, tag="
             rgb = sim.render_view(k, out=view).flip(-1).cpu().numpy()                  # B,G,R -> R,G,B
             for e in range(k):
                 Image.fromarray(rgb[e]).save(os.path.join(frames, "%s_env%d_step%04d.png" % (tag, e, t)))
+        fresh = sim.game_over_codes != 0
         sim.reset_done()                             # `if game_over: reset_game()` for the whole batch
     print("%s: %d envs, %d steps, %d episodes finished, mean reward %.3f, obs %s %s" % (
         name, num_envs, steps, finished, float(total.mean()), tuple(sim.obs.shape), sim.obs.dtype))
+    if expert:
+        perf, _ = sim.task_performance()
+        print("expert policy: %d successes, %d failures; %d of %d episodes (%.1f %%) started without a path" % (
+            sum(v[0] for v in perf.values()), sum(v[1] for v in perf.values()), no_path, started, 100.0 * no_path / max(started, 1)))
     sim.close()
 
 
@@ -77,10 +90,12 @@ if __name__ == "__main__":
     ap.add_argument("games", nargs="*", metavar="|".join(OPTS))
     ap.add_argument("--frames", metavar="DIR", help="write the first K envs' views of every step as PNGs (xworld, xworld_ego)")
     ap.add_argument("--frame-envs", type=int, default=4, metavar="K")
+    ap.add_argument("--policy", choices=["random", "expert"], default="random",
+                    help="expert: xworld batches follow BatchedSimulator.expert (the other games stay random)")
     args = ap.parse_args()
     for w in args.games or list(OPTS):
         if w not in OPTS:
             ap.error("unknown game " + w)
         name, opts = OPTS[w]
         single_env(name, dict(opts))
-        batch(name, dict(opts), frames=args.frames, frame_envs=args.frame_envs, tag=w)
+        batch(name, dict(opts), frames=args.frames, frame_envs=args.frame_envs, tag=w, policy=args.policy)

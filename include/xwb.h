@@ -548,6 +548,49 @@ int xwb_xw_render_grids(xwb_sim *sim, const uint16_t *grids_dev, const uint8_t *
 int xwb_xw_view_dims(const xwb_sim *sim, size_t *h, size_t *w, size_t *c);
 int xwb_xw_render_view(xwb_sim *sim, const int32_t *envs_dev, int32_t n, void *out_dev, size_t out_bytes, void *stream);
 
+/* ---- the shortest-path expert: what the right action is ----
+ * xwb_xw_expert answers, for every env of an XWorld2D batch and for the state the NEXT xwb_step will act on (act_rep 1):
+ *   dist[e]     the smallest number k >= 1 of xwb_step calls after which the batch's XWorld3DNav* task group records
+ *               XWB_EV_CORRECT_GOAL, over all action sequences, nothing but the agent moving; XWB_EXPERT_NO_PATH when there is none
+ *   actions[e]  the first action of such a sequence, the LOWEST action id among several optimal ones; no_path_action where
+ *               dist is XWB_EXPERT_NO_PATH (any value xwb_step accepts, XWB_ACTION_SKIP included -- a skipped env never times out,
+ *               which is the caller's business).  The array is what xwb_step takes.
+ *   field[e][h][y * max_dim + x]  (optional, uint16) the same number with the agent placed on cell (x, y) with heading h; 0xFFFF
+ *               for an occupied cell (the agent's own counts as free), a cell outside the env's actual dims (padding bricks)
+ *               and a node without a path.  h: one plane under full observation (the heading is fixed at +y), four in
+ *               egocentric mode (0 +x, 1 +y, 2 -x, 3 -y, the heading of xwb_env_state).  The agent's own node holds dist.
+ *               xwb_xw_expert_field_dims reports headings and cells; field_dev holds num_envs * headings * cells values.
+ * Success is what the step rule rewards in the navigation stage of an XWorld3DNav* task:
+ *   Target, Near, Avoid  a move ALONG THE HEADING (full observation: MOVE_DOWN; egocentric: MOVE_FORWARD) into a cell that holds
+ *               a goal of the teacher's target set (XWB_CELL_TARGET)
+ *   Direction   the same bump into a goal one cell away from the referent, the direction word holding for the heading at the
+ *               moment of the bump; a replayed map without a referent (target < 0): the target-set rule
+ *   Between     a call that leaves the agent on the middle cell without a goal bumped along the heading: a move onto it -- or,
+ *               for an agent already standing there, any action that keeps it there (a turn, a blocked move)
+ * A goal bumped along the heading that does not win ends the episode (XWB_EV_WRONG_GOAL) for every task: such a bump is never
+ * part of a path, nor a way to stand still.  State graph: full observation, 4 actions, node = cell; egocentric, 6 actions,
+ * node = (cell, heading), a turn costs one step.  A move into an occupied cell or off the map leaves the node unchanged.  The
+ * task's time limit (dims^2 * max_steps_factor) and max_steps are NOT folded in: compare dist with the steps that are left.
+ * XWB_EXPERT_NO_PATH by definition: the group's stage is not the navigation stage (idle, terminal), or the env's game-over
+ * code is set and it has not been reset (its arrays may already hold the next episode, see xwb_reset_done); the field of such
+ * an env is all 0xFFFF.  After xwb_step_autoreset, which keeps the codes but has reset the envs, the new episodes are answered.
+ * Two task groups: the XWorld3DNav* group is followed when it is the batch's FIRST group (confs/nav_two_groups.json), under
+ * exclusive scheduling as well (idle: XWB_EXPERT_NO_PATH).  In second position it is refused (below): run non-exclusively there
+ * it never sees a collision, the first group's stage having consumed the step's events.  Curriculum batches: the actual dims.
+ * actions_dev may be NULL when dist_dev is given; dist_dev and field_dev may be NULL; field_dev 16-byte aligned.
+ * XWB_ERR_ARG, and nothing is launched: a game other than XWorld2D; actions_dev == dist_dev == NULL; a batch whose only
+ * group(s) hold the 2-D-native tasks (XWB_TASK2D_*: they succeed when the agent's cell equals the target, a goal's own cell,
+ * which a move never enters -- no path exists); two groups with the XWorld3DNav* one in second position.  A poisoned batch:
+ * XWB_ERR_STATE.
+ * One kernel launch on `stream`, behind the verbs queued there; no allocation, no copy, no host synchronisation, nothing on the
+ * internal queue.  It reads the state the next step reads -- never a look-ahead snapshot or a pre-generated episode -- and
+ * changes nothing: the next xwb_step's path (xwb_step_path), the snapshot and pre-generation flags and every result of a
+ * rollout are the same with and without calls in between. */
+#define XWB_EXPERT_NO_PATH (-1)
+int xwb_xw_expert_field_dims(const xwb_sim *sim, size_t *headings, size_t *cells);
+int xwb_xw_expert(xwb_sim *sim, int32_t *actions_dev, int32_t *dist_dev, uint16_t *field_dev, int32_t no_path_action,
+                  void *stream);
+
 /* (test and measurement hooks -- xwb_debug_stall_handoff, xwb_profile_begin / _end / _stop -- are not part of this boundary:
  * include/xwb_testing.h, version node XWB_TESTING of csrc/libxwb.map) */
 

@@ -48,6 +48,7 @@ class BatchedSimulator:
             raise RuntimeError("Unrecognized game type: " + name)        # py_simulator.cpp:184-186
         self.L = lib.load()
         self.name = name
+        self._expert_bufs = {}                               # expert(): the tensors it allocates once and reuses
         cfg = lib.XwbConfig()
         lib.check(self.L.xwb_default_config(GAMES[name], C.byref(cfg)))
         cfg.num_envs = int(num_envs)
@@ -461,6 +462,45 @@ class BatchedSimulator:
         if getattr(self, "_view_hwc", None) is None:
             self._view_hwc = self.view_dims
         return self._view_hwc
+
+    @property
+    def expert_field_dims(self):
+        """xwb_xw_expert_field_dims: (headings, cells) of one env's distance field -- (1, max_dim^2) under full observation,
+        (4, max_dim^2) in egocentric mode."""
+        hh, cc = C.c_size_t(), C.c_size_t()
+        lib.check(self.L.xwb_xw_expert_field_dims(self.h, C.byref(hh), C.byref(cc)))
+        return (hh.value, cc.value)
+
+    def expert(self, actions=None, dist=None, field=False, no_path=0, stream=None):
+        """xwb_xw_expert: for the state the next step() acts on, per env the fewest steps after which its XWorld3DNav* task records
+        "correct_goal" (dist, int32; -1 = no path, a finished env, a group outside its navigation stage), the first action of
+        such a path (actions, int32: what step(actions) takes; `no_path` where dist is -1; -1, XWB_ACTION_SKIP, is allowed) and,
+        with field=True or a tensor, the same number for every (heading, cell) the agent could stand on (uint16 [num_envs,
+        headings, max_dim^2], 0xFFFF = none).  Returns (actions, dist) or (actions, dist, field): CUDA tensors allocated on the
+        first call and reused by the later ones unless the caller passes its own.  One kernel launch on `stream`; reads only."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        own = self._expert_bufs
+
+        def buf(name, given, shape, dtype):
+            if given is None or given is True:
+                if name not in own:
+                    own[name] = torch.empty(shape, dtype=dtype, device=dev)
+                return own[name]
+            if not isinstance(given, torch.Tensor) or given.dtype != dtype or given.device != dev or tuple(given.shape) != shape \
+                    or not given.is_contiguous():
+                raise ValueError("%s: a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
+            return given
+
+        n = self.num_envs
+        a = buf("actions", actions, (n,), torch.int32)
+        d = buf("dist", dist, (n,), torch.int32)
+        f = None
+        if field is not False and field is not None:
+            f = buf("field", field, (n,) + tuple(self.expert_field_dims), torch.uint16)
+        lib.check(self.L.xwb_xw_expert(self.h, C.c_void_p(a.data_ptr()), C.c_void_p(d.data_ptr()),
+                                       C.c_void_p(f.data_ptr()) if f is not None else None, int(no_path), self._stream(stream)))
+        return (a, d) if f is None else (a, d, f)
 
     def env_state(self, env=0, stream=None):
         st = lib.XwbEnvState()

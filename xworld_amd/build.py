@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libxwb.so")
-SOURCES = ["kernels_simple.hip", "kernels_xworld.hip", "kernels_xworld_reset.hip", "kernels_xworld_ego.hip", "kernels_xworld_view.hip",
+SOURCES = ["kernels_simple.hip", "kernels_xworld.hip", "kernels_xworld_reset.hip", "kernels_xworld_ego.hip", "kernels_xworld_view.hip", "kernels_xworld_expert.hip",
            "xwb_create.hip", "xwb_verbs.hip", "xwb_getters.hip", "xwb_checkpoint.hip", "xwb_comm.hip",
            "xwb_sentence_ids.hip"]
 HEADERS = [os.path.join(CSRC, "xwb_common.h"), os.path.join(CSRC, "xw_device.h"), os.path.join(CSRC, "xw_ego_cells.h"), os.path.join(CSRC, "xwb_language.h"), os.path.join(CSRC, "xwb_sentence_ids.h"),

@@ -85,6 +85,9 @@ enum : int { ALIVE = 0, MAX_STEP = 1, DEAD = 2, SUCCESS = 4, LOST_LIFE = 8 };
 // XWB_ACTION_SKIP (include/xwb.h): the env does not take part in this step call
 enum : int { ACTION_SKIP = -1 };
 
+// XWB_EXPERT_NO_PATH (include/xwb.h): xwb_xw_expert's dist of an env that cannot win
+enum : int { EXPERT_NO_PATH = -1 };
+
 // which envs a state-changing kernel applies to
 enum : int { MODE_STEP = 0, MODE_RESET_ALL = 1, MODE_RESET_DONE = 2, MODE_RESET_MASK = 3 };
 
@@ -375,6 +378,11 @@ hipError_t launch_xw_pack_grids(const XwParams &p, int src, uint16_t *out_grid, 
 // `out`, slot i = env envs[i] (device memory; NULL: env i; an index outside the batch: zeros).  src: PACK_SRC_*, full observation;
 // view_atlas: xwb_sim::d_view_atlas (full observation; egocentric batches read atlas64 / goal_img)
 hipError_t launch_xw_view(const XwParams &p, int src, const int32_t *envs, int n, const void *view_atlas, void *out, hipStream_t s);
+// the shortest-path expert (kernels_xworld_expert.hip): per env the fewest steps to the XWorld3DNav* group's "correct_goal", the
+// first action of such a path, optionally the field [n][headings][max_dim^2] (16-byte aligned).  The group is the batch's first;
+// ignore_done: the done codes are those of envs already reset
+hipError_t launch_xw_expert(const XwParams &p, int32_t *actions, int32_t *dist, uint16_t *field, int no_path_action, bool ignore_done,
+                            hipStream_t s);
 // full observation: RENDER_ALL / RENDER_ALIVE / RENDER_ALL_TERM (LDS-resident atlas, persistent workgroups), RENDER_LIST (atlas
 // through L2); egocentric: launch_xw_render_ego (RENDER_ALL_TERM draws as RENDER_ALL there)
 hipError_t launch_xw_render(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);

@@ -866,6 +866,42 @@ int xwb_xw_render_view(xwb_sim *s, const int32_t *envs_dev, int32_t n, void *out
     return XWB_OK;
 }
 
+int xwb_xw_expert_field_dims(const xwb_sim *s, size_t *headings, size_t *cells) {
+    if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
+    if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_ARG, "not an xworld batch");
+    if (headings) *headings = s->cfg.visible_radius ? 4 : 1;
+    if (cells) *cells = (size_t)s->cfg.max_dim * (size_t)s->cfg.max_dim;
+    return XWB_OK;
+}
+
+int xwb_xw_expert(xwb_sim *s, int32_t *actions_dev, int32_t *dist_dev, uint16_t *field_dev, int32_t no_path_action, void *stream) {
+    if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
+    XWB_ON_DEVICE(s);
+    XWB_LIVE(s);
+    if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_ARG, "not an xworld batch");
+    if (!actions_dev && !dist_dev) return fail(XWB_ERR_ARG, "actions_dev and dist_dev are both NULL");
+    const XwParams &xw = s->xw;
+    if (xw.group2d && !(xw.n_tasks2 > 0 && !xw.group2d_2))
+        return fail(XWB_ERR_ARG, "the batch has no XWorld3DNav* task group: a 2-D-native task succeeds when the agent's cell equals its "
+                                 "target, which is a goal's own cell and never entered (XMap::move_item), so it has no winning path");
+    if (xw.group2d)
+        return fail(XWB_ERR_ARG, "the XWorld3DNav* task group is the batch's SECOND group: the expert follows it in first position only "
+                                 "(list it first in the conf / tasks; run second and non-exclusively it never sees a collision)");
+    if ((reinterpret_cast<uintptr_t>(actions_dev) | reinterpret_cast<uintptr_t>(dist_dev)) & 3u)
+        return fail(XWB_ERR_ARG, "actions_dev and dist_dev must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(field_dev) & 15u) return fail(XWB_ERR_ARG, "field_dev must be 16-byte aligned");
+    if (xw.max_dim > XW_MAX_DIM) return fail(XWB_ERR_ARG, "max_dim exceeds the expert's boards");
+    // Reads the live state, which only kernels on `stream` write between verbs (the internal queue writes pre-generated episodes
+    // and snapshots; where it regenerates envs -- xwb_reset_done, xwb_step_autoreset -- the verb orders `stream` behind it).  An env
+    // the last xwb_step finished is answered from its game-over code alone, so a later xwb_reset_done's map generator may run
+    // beside this kernel: no event.  That holds because such a reset runs with AUTO_RESET_BY_LIST -- the codes are cleared by the
+    // list render on `stream`, behind this kernel, not by the reset kernel on the internal queue; a reset that cleared done[]
+    // itself beside the caller's queue would need the event xwb_xw_render_view records.  After xwb_step_autoreset the codes are
+    // kept for the caller although the envs have started their next episodes: they are not looked at.
+    HIP_TRY(launch_xw_expert(xw_params(s), actions_dev, dist_dev, field_dev, no_path_action, s->autoreset_done, as_stream(stream)));
+    return XWB_OK;
+}
+
 int xwb_profile_begin(xwb_sim *s) {
     if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
     s->profiling = true;
