@@ -320,8 +320,8 @@ int xwb_xw_grid_dev(xwb_sim *sim, uint16_t **ptr);      /* xworld: uint16[num_en
 int xwb_minstd_state_dev(xwb_sim *sim, uint32_t **ptr); /* XWB_RNG_MINSTD: uint32[num_envs] engine states (else NULL) */
 int xwb_done_count(xwb_sim *sim, void *stream, int32_t *n_done);   /* envs reset by the last reset_done (sync) */
 /* xworld, egocentric: which kernels draw the whole-batch frames: 1 = the span path (cells -> evaluated pixels -> gather,
- * kernels_xworld_ego.hip), 0 = one workgroup per env.  Both are bit-exact; callers that report kernel times need to know
- * which ran.  Radii: XMap::image_masking admits ODD radii only (CHECK, xmap.cpp:277; xwb_create refuses even ones with the same
+ * kernels_xworld_ego_span.hip), 0 = one workgroup per env (kernels_xworld_ego.hip).  Both are bit-exact; callers that report
+ * kernel times need to know which ran.  Radii: XMap::image_masking admits ODD radii only (CHECK, xmap.cpp:277; xwb_create refuses even ones with the same
  * words) and XWorldSimulator::init clips the radius to the map's edge (xworld_simulator.cpp:62-68), so r is one of 1, 3, ..., 15.
  * The span path draws r = 3, 5, 7 -- squares of 28, 16 and 12 pixels -- on every map size.  The per-env kernel
  * (XWB_PATH_EGO_PER_ENV) is what draws, and the only thing that can draw:

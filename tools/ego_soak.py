@@ -2,10 +2,11 @@
 env (debug ego_no_span) must draw the same frames through step / reset_done / step_autoreset -- 8192 envs x 200 steps per case:
 r = 3 / 5 / 7, colour and gray, context rings, float32 frames, curriculum, no wall shadows.  python tools/ego_soak.py (on a GPU)"""
 import os, sys, itertools
-sys.path.insert(0, '/root/repo')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import torch
 from xworld_amd.batched import BatchedSimulator
-CONF = '/root/repo/xworld_amd/confs/'
+CONF = os.path.join(ROOT, 'xworld_amd', 'confs') + os.sep
 def make(opts, n, seed, no_span):
     s = BatchedSimulator('xworld', dict(opts, debug=['ego_no_span'] if no_span else []), num_envs=n, seed=seed, policy_seed=seed + 1)
     return s

@@ -12,12 +12,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libxwb.so")
-SOURCES = ["kernels_simple.hip", "kernels_xworld.hip", "kernels_xworld_reset.hip", "kernels_xworld_ego.hip", "kernels_xworld_view.hip", "kernels_xworld_expert.hip",
-           "xwb_create.hip", "xwb_verbs.hip", "xwb_getters.hip", "xwb_checkpoint.hip", "xwb_comm.hip",
+SOURCES = ["kernels_simple.hip", "kernels_xworld.hip", "kernels_xworld_reset.hip", "kernels_xworld_ego.hip", "kernels_xworld_ego_span.hip",
+           "kernels_xworld_view.hip", "kernels_xworld_expert.hip",
+           "xwb_create.hip", "xwb_ego_tables.hip", "xwb_verbs.hip", "xwb_getters.hip", "xwb_checkpoint.hip", "xwb_comm.hip",
            "xwb_sentence_ids.hip"]
-HEADERS = [os.path.join(CSRC, "xwb_common.h"), os.path.join(CSRC, "xw_device.h"), os.path.join(CSRC, "xw_ego_cells.h"), os.path.join(CSRC, "xwb_language.h"), os.path.join(CSRC, "xwb_sentence_ids.h"),
-           os.path.join(CSRC, "xwb_sim.h"),
-           os.path.join(os.path.dirname(HERE), "include", "xwb.h")]
+# every object depends on every header: the headers source_fingerprint hashes
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(HERE), "include", "xwb.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-fvisibility=hidden", "-fvisibility-inlines-hidden"]
 

@@ -7,7 +7,7 @@
 //   egocentric         XMap::to_image(agent, false, r), xmap.cpp:148-200: the [64 r][64 r] window in front of the agent, wall
 //                      shadows black, turned by 90 + yaw degrees.  The cell table is the frame render's (xw_ego_cells.h); a
 //                      view pixel is ONE source pixel: undo the quarter turn (the integer map of ego_pixel,
-//                      kernels_xworld_ego.hip: source index S falls outside and leaves one black row / column), look the cell
+//                      xw_ego_pixel.h: source index S falls outside and leaves one black row / column), look the cell
 //                      up, load one dword of atlas64 / goal_img.  Sources hold 4 bytes per pixel, the view 3: a lane makes
 //                      four pixels = three dwords, one 12-byte store; a wavefront stores 768 contiguous bytes of a row.
 // Both are pure store streams (786 KB per env at 8 x 8, 307 KB at r = 5) whose sources stay in the caches; stores are

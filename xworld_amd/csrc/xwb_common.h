@@ -126,7 +126,7 @@ enum RenderMode : int {
     RENDER_LIST = 1,             // the envs of the compacted done list
     RENDER_ALIVE = 2,            // every env whose done code is 0 (the rest follows as a list)
     RENDER_ALL_TERM = 3,         // every env, those the step just finished from their terminal snapshot (term_grid)
-    RENDER_SPAN_STEP = 4,        // egocentric span path: a step's frames (kernels_xworld_ego.hip ego_span_render)
+    RENDER_SPAN_STEP = 4,        // egocentric span path: a step's frames (kernels_xworld_ego_span.hip ego_span_render)
     // the span path's list render in parts (ego_span_render_list):
     RENDER_LIST_FRONT = 5,       // its two front kernels
     RENDER_LIST_GATHER = 6,      // its gather
@@ -268,14 +268,14 @@ struct XwParams {
     uint8_t *ego_cache;          // nullable (not enough free memory: every goal cell is evaluated every frame)
     uint32_t *ego_cache_valid;
     uint32_t ego_cache_entry, ego_cache_words;
-    // egocentric, span path (kernels_xworld_ego.hip: cells -> misses -> gather), nullable / 0 when the geometry rules it out
+    // egocentric, span path (kernels_xworld_ego_span.hip: cells -> misses -> gather), nullable / 0 when the geometry rules it out
     int ego_span;                // the view cells' pixel rectangles tile the frame in equal squares (no straddling rows / columns)
     uint32_t *ego_cellinfo;      // [n][r * r] what each square of the frame shows (xw_ego_cells_kernel has the bit layout)
     const uint8_t *ego_cls;      // [n_icons + 2] dense index of the images that are the same in every env (blocks, agents, an
                                  //     empty cell, a black one), 0xff: a goal;  ego_cls_icon [ego_ncls]: class -> table slot
     const uint16_t *ego_cls_icon;
     int ego_ncls;
-    const uint8_t *ego_tab3;     // [heading][class c][class a][class l][channel][square] squares (kernels_xworld_ego.hip, EgoSq)
+    const uint8_t *ego_tab3;     // [heading][class c][class a][class l][channel][square] squares (kernels_xworld_ego_span.hip, EgoSq)
     const uint8_t *ego_flat;     // [heading][c][a][l][square]: that entry of ego_tab3 is one flat colour: 1 = 255 (empty cells), 2 = 0 (outside
                                  //     the map, shadow); found by scanning the table once.  The gather reads such squares from ONE shared
                                  //     128-byte line (ego_constline: 128 x 0xff, 128 x 0x00), which stays in every CU's L1 -- two thirds of a
@@ -386,15 +386,30 @@ hipError_t launch_xw_expert(const XwParams &p, int32_t *actions, int32_t *dist, 
 // full observation: RENDER_ALL / RENDER_ALIVE / RENDER_ALL_TERM (LDS-resident atlas, persistent workgroups), RENDER_LIST (atlas
 // through L2); egocentric: launch_xw_render_ego (RENDER_ALL_TERM draws as RENDER_ALL there)
 hipError_t launch_xw_render(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);
-// RENDER_SPAN_STEP and RENDER_LIST_* need the span path; the events are RENDER_SPAN_STEP's (kernels_xworld_ego.hip ego_span_render)
+// The egocentric render.  launch_xw_render_ego (kernels_xworld_ego.hip) is what the verbs call: it draws on the span path
+// (kernels_xworld_ego_span.hip) where xw_ego_span says the geometry allows, else with one workgroup per env.
+// RENDER_SPAN_STEP and RENDER_LIST_* need the span path; the events are RENDER_SPAN_STEP's (launch_xw_ego_span_render)
 hipError_t launch_xw_render_ego(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);
 bool xw_ego_span(const XwParams &p);
+// the span path's two renders (xw_ego_span(p) holds): RENDER_ALL / RENDER_ALIVE / RENDER_SPAN_STEP, and the RENDER_LIST* modes
+hipError_t launch_xw_ego_span_render(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front, hipEvent_t ev_list, hipEvent_t ev_cells);
+hipError_t launch_xw_ego_span_render_list(const XwParams &p, RenderMode mode, hipStream_t s);
 hipError_t launch_xw_warp_goals(const XwParams &p, bool list, hipStream_t s);
 struct EgoTap;
+// xwb_ego_tables.hip (host only): the resize taps, layout tables and square maps of a geometry, uploaded as one blob (EgoBlob)
 hipError_t xw_ego_tables(int r, int max_dim, int out_dim, EgoTap **dev_out, int *fast_out, int *cell_edge_out, int *span_out);
 size_t xw_ego_cache_entry_bytes(const XwParams &p, int cell_edge);
 size_t xw_ego_tab_bytes(const XwParams &p);
 hipError_t launch_xw_ego_build_tab(const XwParams &p, hipStream_t s);
+// A square of the span path's sources (ego_tab3, the goal-cell cache): the U x U pixels one view cell occupies in the frame,
+// per channel [U rows][UP bytes], rows padded to whole 16-byte pieces.  plane: the bytes of one channel of one square.
+struct EgoSquare { int U, UP, plane; };
+constexpr EgoSquare ego_square(int r) { return EgoSquare{84 / r, 4 * ((84 / r / 4 + 3) & ~3), (84 / r) * (4 * ((84 / r / 4 + 3) & ~3))}; }
+// bytes of one goal-cell cache entry on the span path: the square in every channel, then the BELOW and RIGHT lines ([channel][U]
+// each) and the DIAG pixel ([channel]) beside it (kernels_xworld_ego_span.hip, EgoEntry)
+constexpr int ego_square_entry_bytes(int channels, int r) {
+    return (channels * ego_square(r).plane + 2 * channels * ego_square(r).U + 4 + 15) & ~15;
+}
 size_t xw_ego_square_tab_bytes(const XwParams &p);
 size_t xw_ego_square_entry_bytes(const XwParams &p);
 size_t xw_ego_xtab_bytes(const XwParams &p);

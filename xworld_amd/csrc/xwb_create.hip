@@ -472,8 +472,8 @@ int xw_setup(xwb_sim *s) {
         if (p.ego_cellinfo) {
             // which squares of the table are one flat colour (empty cells: 255; outside the map / shadow: 0): found by looking
             // at the table itself, so the shortcut the gather takes for them (XwParams::ego_flat) cannot change a byte
-            const int r = c.visible_radius, U = 84 / r, UP = 4 * ((U / 4 + 3) & ~3), RR = r * r, nc = p.ego_ncls;
-            const size_t CBP = (size_t)U * UP, PBP = (size_t)RR * CBP, keys = (size_t)4 * nc * nc * nc;
+            const int r = c.visible_radius, U = ego_square(r).U, UP = ego_square(r).UP, RR = r * r, nc = p.ego_ncls;
+            const size_t CBP = (size_t)ego_square(r).plane, PBP = (size_t)RR * CBP, keys = (size_t)4 * nc * nc * nc;
             std::vector<uint8_t> tab(xw_ego_square_tab_bytes(p)), flat(keys * RR, 0);
             HIP_TRY(hipMemcpy(tab.data(), s->d_ego_tab3, tab.size(), hipMemcpyDeviceToHost));
             for (size_t k = 0; k < keys; ++k)

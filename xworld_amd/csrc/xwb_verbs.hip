@@ -440,7 +440,7 @@ int step_fused(xwb_sim *s, XwParams &p, bool epochs, hipStream_t st) {
 // (step kernel) from which the big render draws their last frame, so a following xwb_reset_done can regenerate the live state
 // beside that render right away (lazy: nothing rewrites the live grid beside it).  The egocentric render reads more than the grid
 // (heading, goal images): there the terminal frames are rendered from the (short) list on the side stream, beside the big render,
-// which skips those envs; a following xwb_reset_done queues behind that list render.  On the span path (kernels_xworld_ego.hip)
+// which skips those envs; a following xwb_reset_done queues behind that list render.  On the span path (kernels_xworld_ego_span.hip)
 // only the front kernels read the env state: its hand-overs are published behind them, the terminal frames leave through a short
 // list gather and the big gather skips them.
 int step_plain(xwb_sim *s, XwParams &p, bool epochs, int path, hipStream_t st) {
