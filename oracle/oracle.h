@@ -23,9 +23,9 @@
  *   - maze / BFS / maps / NavTarget teacher: pinned by golden vectors produced
  *     by importing the reference's Python modules in the build container
  *     (tests/golden/make_golden.py)
- *   - SimpleRace           no reference test exists and the reference C++
- *     cannot be built here without stand-in headers: pinned only by the
- *     known-answer values recorded in SURVEY.md 8(a) -> "parity partially pinned"
+ *   - SimpleRace, SimpleGame, the minstd reset draws: bit for bit against a build of
+ *     the reference's own sources (make ref -> oracle/_ref/libxwref.so,
+ *     tests/test_ref_simple.py) and its recorded results (tests/golden/ref_simple_*.json)
  *   - XWorld2D pixels      OpenCV 3.2.0 is absent: the resize / BGR2GRAY
  *     arithmetic is restated from the library's published algorithm ->
  *     "parity unpinned" for pixel values (bit-exact vs this restatement only)

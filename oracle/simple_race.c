@@ -14,9 +14,9 @@
  * cv::Point_ operators narrow with saturate_cast<float>.  This file must be
  * compiled with -ffp-contract=off (no FMA contraction), see oracle/Makefile.
  *
- * Pinning: the reference has no SimpleRace test and its C++ cannot be built
- * here without stand-in headers -> pinned only by the known-answer values in
- * SURVEY.md 8(a) (tests/test_oracle_simple_race.py).
+ * Pinning: bit for bit against a build of the reference's own sources
+ * (oracle/_ref/libxwref.so, `make ref`; tests/test_ref_simple.py) and its
+ * recorded results (tests/golden/ref_simple_race.json); docs/pinning.md.
  */
 #include "oracle.h"
 #include <math.h>

@@ -183,8 +183,9 @@ def test_simple_race_rollout(oracle, case, trig):
     sim.close()
 
 
-def test_simple_race_kat_survey_reward_unpinned_by_reference(oracle):
-    """SURVEY.md 8(a) known answers (straight defaults, legal actions {4,7}) through the product."""
+def test_simple_race_kat_survey_reward(oracle):
+    """SURVEY.md 8(a) known answers (straight defaults, legal actions {4,7}) through the product.  The reward is pinned by a
+    build of the reference's own sources since tests/test_ref_simple.py / tests/test_gpu_ref_simple.py."""
     torch = _torch()
     from xworld_amd.batched import BatchedSimulator
     sim = BatchedSimulator("simple_race", _race_opts({}), num_envs=2)

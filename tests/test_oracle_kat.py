@@ -4,7 +4,8 @@
   tests/test_simulator_seed.cpp:22-50          thread-local RNG sequences for FLAGS_simulator_seed 1 and 2
   tests/test_statepacket.cpp:77-104            StatePacket serialisation round trip
 plus the known-answer values recorded in SURVEY.md 8(a) for SimpleGame contexts and SimpleRace
-(the reference has no SimpleRace test and its C++ cannot be built here; see oracle/oracle.h).
+(the reference has no SimpleRace test; the oracle's SimpleGame / SimpleRace are also pinned to a build of the reference's own
+sources, tests/test_ref_simple.py).
 """
 import ctypes as C
 
@@ -89,7 +90,7 @@ def test_philox_known_answers(oracle):
         [0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1]
 
 
-def test_simple_race_survey_kats_reward_unpinned_by_reference(oracle):
+def test_simple_race_survey_kats_reward(oracle):
     r = oracle.SimpleRace()
     r.reset_game()
     exp_obs = [(1, 0, 0, -0.800000012), (0.95105654, -0.309016943, -0.0309020989, -0.780978978),
