@@ -2,11 +2,14 @@
 """Random-policy rollouts, the shape of the reference's python/examples/test_*.py -- once through the
 py_simulator-compatible object (one env, Python dicts), once through the batch API (device tensors).
 
-    python examples/rollout.py [simple_game|simple_race|xworld|xworld_ego] [--frames DIR [--frame-envs K]]
+    python examples/rollout.py [simple_game|simple_race|xworld|xworld_ego] [--frames DIR [--frame-envs K]] [--symbolic]
 
 --frames DIR (xworld, xworld_ego): the batch rollout also writes the first K envs' views of every step (render_view: the
 64-pixel-per-cell image behind the observation) as DIR/<game>_env<e>_step<t>.png -- what take_actions(..., show_screen=True)
 put into a window.  Views are B,G,R like the reference's cv::Mat; they are flipped to R,G,B for the PNG here.
+
+--symbolic (xworld, xworld_ego): the batch rollout prints env 0's symbolic observation at every step -- the KIND plane of
+BatchedSimulator.symbolic() as characters ('.' empty, 'G' goal, '#' block, 'A' agent, ' ' dark) beside the teacher's sentence.
 """
 import os
 import random
@@ -45,9 +48,22 @@ def single_env(name, opts, steps=200):
                                                                        game.get_screen_out_dimensions()))
 
 
-def batch(name, opts, num_envs=4096, steps=200, frames=None, frame_envs=4, tag="", policy="random"):
+SYM_CHARS = ".G#A "                                   # SYM_EMPTY, SYM_GOAL, SYM_BLOCK, SYM_AGENT, SYM_DARK
+
+
+def print_symbolic(sim, t):
+    """env 0: the KIND plane as characters, the teacher's sentence beside its first line"""
+    from xworld_amd.batched import SYM_PLANE_KIND
+    kind = sim.symbolic()[0, SYM_PLANE_KIND].cpu().numpy()
+    sentence = sim.sentence(0) or "-"
+    for i, row in enumerate(kind):
+        print("symbolic step %3d  |%s|%s" % (t, "".join(SYM_CHARS[v] for v in row), "  teacher: " + sentence if i == 0 else ""))
+
+
+def batch(name, opts, num_envs=4096, steps=200, frames=None, frame_envs=4, tag="", policy="random", symbolic=False):
     import torch
     sim = BatchedSimulator(name, opts, num_envs=num_envs)
+    symbolic = symbolic and name == "xworld"
     view = None
     if frames and name == "xworld":
         from PIL import Image
@@ -73,6 +89,8 @@ def batch(name, opts, num_envs=4096, steps=200, frames=None, frame_envs=4, tag="
             rgb = sim.render_view(k, out=view).flip(-1).cpu().numpy()                  # B,G,R -> R,G,B
             for e in range(k):
                 Image.fromarray(rgb[e]).save(os.path.join(frames, "%s_env%d_step%04d.png" % (tag, e, t)))
+        if symbolic:                                 # (before the reset, like the views)
+            print_symbolic(sim, t)
         fresh = sim.game_over_codes != 0
         sim.reset_done()                             # `if game_over: reset_game()` for the whole batch
     print("%s: %d envs, %d steps, %d episodes finished, mean reward %.3f, obs %s %s" % (
@@ -92,10 +110,13 @@ if __name__ == "__main__":
     ap.add_argument("--frame-envs", type=int, default=4, metavar="K")
     ap.add_argument("--policy", choices=["random", "expert"], default="random",
                     help="expert: xworld batches follow BatchedSimulator.expert (the other games stay random)")
+    ap.add_argument("--symbolic", action="store_true", help="print env 0's symbolic observation at every step (xworld, xworld_ego)")
+    ap.add_argument("--steps", type=int, default=200, metavar="N", help="steps of each rollout")
     args = ap.parse_args()
     for w in args.games or list(OPTS):
         if w not in OPTS:
             ap.error("unknown game " + w)
         name, opts = OPTS[w]
-        single_env(name, dict(opts))
-        batch(name, dict(opts), frames=args.frames, frame_envs=args.frame_envs, tag=w, policy=args.policy)
+        single_env(name, dict(opts), steps=args.steps)
+        batch(name, dict(opts), steps=args.steps, frames=args.frames, frame_envs=args.frame_envs, tag=w, policy=args.policy,
+              symbolic=args.symbolic)

@@ -591,6 +591,38 @@ int xwb_xw_expert_field_dims(const xwb_sim *sim, size_t *headings, size_t *cells
 int xwb_xw_expert(xwb_sim *sim, int32_t *actions_dev, int32_t *dist_dev, uint16_t *field_dev, int32_t no_path_action,
                   void *stream);
 
+/* ---- symbolic observations: what each square of the frame shows ----
+ * xwb_xw_symbolic writes, for EVERY env of an XWorld2D batch, what the agent can see as ids instead of pixels: out_dev is
+ * int16 [num_envs][XWB_SYM_PLANES][S][S], planar like the frames; xwb_xw_symbolic_dims reports 3, S, S.
+ *   full observation   S = max_dim; entry [i][j] is map cell (x = j, y = i) = rows [12 i, 12 i + 12) x columns [12 j, 12 j + 12)
+ *                      of the frame
+ *   egocentric         S = r; entry [i][j] is the square rows [i p, (i + 1) p) x columns [j p, (j + 1) p), p = 84 / r, of the frame:
+ *                      the window in front of the agent, turned by quarter turns so that the agent faces up (it stands in the
+ *                      bottom-centre square).  The reference's turn shifts the picture by one pixel line for three of the four
+ *                      headings, so a square is one window cell's image apart from one line; [i][j] names that cell.  Every
+ *                      odd r the batch accepts.
+ * It describes the frame xwb_xw_render_view describes, by the same rules: an env the last xwb_step finished and that has not
+ * been reset shows its terminal state on every step path (lazy, fused, classic, autoreset); after xwb_step_autoreset it shows the
+ * new episode; look-ahead snapshots and pre-generated episodes never show; with xwb_xw_set_draw(sim, 0) it is what
+ * xwb_xw_pack_grids reports.
+ *   plane XWB_SYM_PLANE_KIND  XWB_SYM_EMPTY; XWB_SYM_GOAL / _BLOCK / _AGENT = the XWB_ICON_* type of the cell's icon + 1 (the
+ *                      padding bricks around a curriculum env smaller than max_dim are blocks, as in the frame); XWB_SYM_DARK:
+ *                      a square the frame draws black -- outside the map, or in a wall's shadow unless no_wall_shadow (one
+ *                      value: the frame does not tell them apart either)
+ *   plane XWB_SYM_PLANE_ICON  the palette index, (cell code & XWB_CELL_ICON_MASK) - 1; -1 for EMPTY and DARK.  XWB_CELL_TARGET,
+ *                      the teacher's answer, never appears
+ *   plane XWB_SYM_PLANE_NAME  icon_name[icon], the id xwb_set_names and the sentences bind; -1 where ICON is -1
+ * out_bytes: the size of out_dev (2-byte aligned).  XWB_ERR_ARG, and nothing is launched: a game other than XWorld2D, out_dev
+ * NULL, out_bytes smaller than num_envs observations.  A poisoned batch: XWB_ERR_STATE.
+ * One kernel launch on `stream`, behind the verbs queued there; no allocation, no copy, no host synchronisation.  It reads; it
+ * changes no state: xwb_step_path, the snapshot and pre-generation flags, shadow_breaks and every result of a rollout are the
+ * same with and without calls in between.  (Egocentric batches: one event orders the internal queue's LATER work behind the
+ * kernel, as for xwb_xw_render_view.)  Cost: 6 S^2 bytes per env -- 54 at r = 3, 294 at r = 7, 384 at 8 x 8. */
+enum { XWB_SYM_EMPTY = 0, XWB_SYM_GOAL = 1, XWB_SYM_BLOCK = 2, XWB_SYM_AGENT = 3, XWB_SYM_DARK = 4 };
+enum { XWB_SYM_PLANE_KIND = 0, XWB_SYM_PLANE_ICON = 1, XWB_SYM_PLANE_NAME = 2, XWB_SYM_PLANES = 3 };
+int xwb_xw_symbolic_dims(const xwb_sim *sim, size_t *planes, size_t *rows, size_t *cols);
+int xwb_xw_symbolic(xwb_sim *sim, int16_t *out_dev, size_t out_bytes, void *stream);
+
 /* (test and measurement hooks -- xwb_debug_stall_handoff, xwb_profile_begin / _end / _stop -- are not part of this boundary:
  * include/xwb_testing.h, version node XWB_TESTING of csrc/libxwb.map) */
 

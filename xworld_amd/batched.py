@@ -14,6 +14,10 @@ from .lib import XWB_SIMPLE_GAME, XWB_SIMPLE_RACE, XWB_XWORLD2D
 
 GAMES = {"simple_game": XWB_SIMPLE_GAME, "simple_race": XWB_SIMPLE_RACE, "xworld": XWB_XWORLD2D}
 
+# include/xwb.h XWB_SYM_*: the KIND plane's values and the planes of BatchedSimulator.symbolic()
+SYM_EMPTY, SYM_GOAL, SYM_BLOCK, SYM_AGENT, SYM_DARK = 0, 1, 2, 3, 4
+SYM_PLANE_KIND, SYM_PLANE_ICON, SYM_PLANE_NAME, SYM_PLANES = 0, 1, 2, 3
+
 
 class _DevArray:
     """Zero-copy view of library-owned device memory through __cuda_array_interface__."""
@@ -501,6 +505,37 @@ class BatchedSimulator:
         lib.check(self.L.xwb_xw_expert(self.h, C.c_void_p(a.data_ptr()), C.c_void_p(d.data_ptr()),
                                        C.c_void_p(f.data_ptr()) if f is not None else None, int(no_path), self._stream(stream)))
         return (a, d) if f is None else (a, d, f)
+
+    @property
+    def symbolic_dims(self):
+        """xwb_xw_symbolic_dims: (3, S, S) of one env's symbolic observation -- S = max_dim under full observation, the visible
+        radius in egocentric mode."""
+        pp, rr, cc = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        lib.check(self.L.xwb_xw_symbolic_dims(self.h, C.byref(pp), C.byref(rr), C.byref(cc)))
+        return (pp.value, rr.value, cc.value)
+
+    def symbolic(self, out=None, stream=None):
+        """xwb_xw_symbolic: what each square of every env's newest frame shows, as ids -- int16 CUDA tensor [num_envs, 3, S, S],
+        planes SYM_PLANE_KIND (SYM_EMPTY, SYM_GOAL, SYM_BLOCK, SYM_AGENT; SYM_DARK where the frame is black: outside the map or in
+        a wall's shadow), SYM_PLANE_ICON (palette index, -1 for empty and dark squares) and SYM_PLANE_NAME (the name id the
+        sentences use, -1 likewise).  Full observation: [i][j] is map cell (x = j, y = i); egocentric: the window turned so that
+        the agent faces up and stands in the bottom-centre square.  The teacher's target marks never appear.  The tensor is
+        allocated on the first call and reused by the later ones unless the caller passes `out` (contiguous, int16, that shape,
+        on the batch's device; ValueError otherwise).  One kernel launch on `stream`; reads only."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if getattr(self, "_sym_dims", None) is None:
+            self._sym_dims = self.symbolic_dims
+        shape = (self.num_envs,) + tuple(self._sym_dims)
+        if out is None:
+            if getattr(self, "_sym_buf", None) is None:
+                self._sym_buf = torch.empty(shape, dtype=torch.int16, device=dev)
+            out = self._sym_buf
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.int16 or out.device != dev or tuple(out.shape) != shape \
+                or not out.is_contiguous():
+            raise ValueError("out: a contiguous int16 tensor of shape %s on %s" % (shape, dev))
+        lib.check(self.L.xwb_xw_symbolic(self.h, C.c_void_p(out.data_ptr()), out.numel() * 2, self._stream(stream)))
+        return out
 
     def env_state(self, env=0, stream=None):
         st = lib.XwbEnvState()

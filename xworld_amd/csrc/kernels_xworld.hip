@@ -861,8 +861,8 @@ __global__ __launch_bounds__(256) void xw_pack_grids_kernel(XwParams p, int src,
     const size_t gi = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (gi >= (size_t)p.n * cells) return;
     const int e = (int)(gi / cells);
-    const bool term = src == PACK_SRC_TERM && p.term_flag[e];
-    out_grid[gi] = (term ? p.term_grid[gi] : p.grid[gi]) & CELL_ICON_MASK;
+    const bool term = xw_frame_is_term(p, src, e);
+    out_grid[gi] = xw_frame_code(p, term, gi);
     if (out_flag && gi == (size_t)e * cells) {
         const bool at_start = p.num_steps[e] == 0;
         out_flag[e] = (uint8_t)(src == PACK_SRC_LIST ? (at_start ? 2 : 0) : (term ? 1 : (at_start ? 2 : p.fresh[e])));

@@ -49,9 +49,9 @@ __global__ __launch_bounds__(VIEW_BS) void xw_view_full_kernel(XwParams p, int s
     }
     __shared__ uint32_t s_entry[XW_MAX_DIM];                                    // atlas entry of each cell of this cell row
     if (tid < D) {
-        const bool term = src == PACK_SRC_TERM && p.term_flag[e];
+        const bool term = xw_frame_is_term(p, src, e);
         const size_t gi = (size_t)e * cells + cy * (unsigned)D + tid;
-        s_entry[tid] = (uint32_t)((term ? p.term_grid[gi] : p.grid[gi]) & CELL_ICON_MASK) * (64u * 12u);
+        s_entry[tid] = xw_frame_code(p, term, gi) * (64u * 12u);
     }
     __syncthreads();
     // piece t of the band: pixel row t / row_pieces, piece j = t % row_pieces of that row (advanced without a division)
@@ -101,18 +101,15 @@ __global__ __launch_bounds__(VIEW_BS) void xw_view_ego_kernel(XwParams p, const 
     __syncthreads();
     const uint32_t *black = atlas4 + (size_t)p.n_icons * 4096 + 1;
     typedef const uint32_t __attribute__((address_space(1))) *global_u32;       // (pointers out of LDS: say they are global)
-    const bool row_is_y = dir == 3 || dir == 1;
     const int dq = VIEW_BS % row_quads, dr = VIEW_BS / row_quads;
     int vr = tid / row_quads, q = tid - vr * row_quads;
     vr += 64 * (int)band;
     for (int t = tid; t < band_quads; t += VIEW_BS) {
-        // up (3): sx = vc, sy = vr;  right (0): sx = S - vr, sy = vc;  down (1): sx = S - vc, sy = S - vr;  left (2): sx = vr, sy = S - vc
-        const int fr = (dir == 3 || dir == 2) ? vr : S - vr;
         uint32_t v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int vc = 4 * q + i, fc = (dir == 3 || dir == 0) ? vc : S - vc;
-            const int sx = row_is_y ? fc : fr, sy = row_is_y ? fr : fc;
+            int sx, sy;
+            ego_view_source(dir, S, vr, 4 * q + i, &sx, &sy);
             const bool inview = (unsigned)sx < (unsigned)S && (unsigned)sy < (unsigned)S;
             const EgoCell cell = s_cells[inview ? (sy >> 6) * r + (sx >> 6) : 0];
             const uint32_t *src = inview ? cell.img + ((((sy & 63) << 6) | (sx & 63)) & cell.mask) : black;

@@ -27,6 +27,14 @@ __device__ __forceinline__ int task_kind(int ts) { return (ts >> 24) & 0xf; }
 // cell code: bits 0..14 = palette icon + 1 (0 = empty), bit 15 = the goal belongs to the teacher's target set
 constexpr uint32_t CELL_ICON_MASK = 0x7fffu, CELL_TARGET_BIT = 0x8000u;
 
+// What env e's newest full-observation frame was drawn from (src: PACK_SRC_*, what the last frame-drawing verb read): the
+// terminal snapshot of an env the classic xwb_step just finished, else the live grid -- the one statement of that selection,
+// for xwb_xw_pack_grids, xwb_xw_render_view and xwb_xw_symbolic.  The code comes without the target bit.
+__device__ __forceinline__ bool xw_frame_is_term(const XwParams &p, int src, int e) { return src == PACK_SRC_TERM && p.term_flag[e]; }
+__device__ __forceinline__ uint32_t xw_frame_code(const XwParams &p, bool term, size_t gi) {
+    return (term ? p.term_grid[gi] : p.grid[gi]) & CELL_ICON_MASK;
+}
+
 // The idle stage of a 2-D-native task (XWorldNavTarget.py:22-33, XWorldNavColorTarget.py:8-20; Near / Between never
 // find a target in this snapshot): Task::reset, then a uniformly chosen reachable [coloured] goal.
 // `draw(n)` supplies the decisions (reset stream at reset time, stream 2 / block = num_steps at step time).

@@ -1,7 +1,8 @@
 // xw_ego_cells.h -- what the r x r cells in front of an egocentric agent show (XMap::to_image with visible_radius > 0,
 // xmap.cpp:148-200): the wall shadows of XMap::image_masking and the table view cell -> image.  Device code shared by the
-// one-workgroup-per-env frame render (kernels_xworld_ego.hip, xw_render_ego_kernel) and the native-resolution view
-// (kernels_xworld_view.hip): one wavefront walks one env, its scratch arrays live in LDS.
+// one-workgroup-per-env frame render (kernels_xworld_ego.hip, xw_render_ego_kernel), the native-resolution view
+// (kernels_xworld_view.hip) and the symbolic observation (kernels_xworld_symbolic.hip): one wavefront walks one env, its
+// scratch arrays live in LDS.
 #pragma once
 #include "xwb_common.h"
 
@@ -68,6 +69,16 @@ __device__ __forceinline__ EgoWindow ego_image_masking(int r, int ax, int ay, in
     return EgoWindow{x_st, y_st};
 }
 
+// The quarter turn of the view undone (cv::warpAffine by 90 + yaw degrees, an exact integer map): pixel (row vr, column vc) of
+// the turned S x S view shows pixel (*sx, *sy) of the window; an index S falls outside and leaves one black row / column.
+//   up (3): sx = vc, sy = vr;  right (0): sx = S - vr, sy = vc;  down (1): sx = S - vc, sy = S - vr;  left (2): sx = vr, sy = S - vc
+__device__ __forceinline__ void ego_view_source(int dir, int S, int vr, int vc, int *sx, int *sy) {
+    const int fr = (dir == 3 || dir == 2) ? vr : S - vr, fc = (dir == 3 || dir == 0) ? vc : S - vc;
+    const bool row_is_y = dir == 3 || dir == 1;
+    *sx = row_is_y ? fc : fr;
+    *sy = row_is_y ? fr : fc;
+}
+
 // What view cell k shows.  code / type: the env's grid (target bit stripped) and the type of the entity in each cell (3 = none);
 // gc: its goal slot -> cell table; gimg: its warped goal images.  *slot: the goal slot of a goal, -1 for everything else.
 __device__ __forceinline__ EgoCell ego_window_cell(const XwParams &p, const uint32_t *atlas4, const uint8_t *icon_type,
@@ -95,6 +106,10 @@ __device__ __forceinline__ EgoCell ego_window_cell(const XwParams &p, const uint
     }
     return c;
 }
+
+// Which entry of the table frames a view cell shows (EgoCell::tab without the heading): icon i < n_icons, n_icons = an empty
+// cell, n_icons + 1 = a black one (outside the map, a wall's shadow); -1: a goal
+__device__ __forceinline__ int ego_cell_entry(const EgoCell &c) { return c.tab >> 2; }
 
 }  // namespace
 }  // namespace xwb

@@ -383,6 +383,9 @@ hipError_t launch_xw_view(const XwParams &p, int src, const int32_t *envs, int n
 // ignore_done: the done codes are those of envs already reset
 hipError_t launch_xw_expert(const XwParams &p, int32_t *actions, int32_t *dist, uint16_t *field, int no_path_action, bool ignore_done,
                             hipStream_t s);
+// symbolic observations (kernels_xworld_symbolic.hip): int16 [n][3][S][S], S = max_dim or visible_radius -- what each square of
+// every env's newest frame shows (planes XWB_SYM_PLANE_*).  src: PACK_SRC_*, full observation
+hipError_t launch_xw_symbolic(const XwParams &p, int src, int16_t *out, hipStream_t s);
 // full observation: RENDER_ALL / RENDER_ALIVE / RENDER_ALL_TERM (LDS-resident atlas, persistent workgroups), RENDER_LIST (atlas
 // through L2); egocentric: launch_xw_render_ego (RENDER_ALL_TERM draws as RENDER_ALL there)
 hipError_t launch_xw_render(const XwParams &p, RenderMode mode, hipStream_t s, hipEvent_t ev_front = nullptr, hipEvent_t ev_list = nullptr, hipEvent_t ev_cells = nullptr);

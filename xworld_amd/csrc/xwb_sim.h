@@ -100,7 +100,7 @@ struct xwb_sim {
     uint32_t *h_poison = nullptr;          // pinned host word: a watchdog expired (XwParams::poison_host points at it)
     bool poisoned = false;
     hipEvent_t ev_step = nullptr, ev_reset = nullptr, ev_term = nullptr, ev_cells = nullptr;
-    hipEvent_t ev_view = nullptr;          // egocentric xwb_xw_render_view: the internal queue's later work follows the view kernel
+    hipEvent_t ev_view = nullptr;          // egocentric xwb_xw_render_view / xwb_xw_symbolic: the internal queue's later work follows their kernel
     hipEvent_t ev_results = nullptr;       // xwb_gather_results_beside's hand-over when the last step did not run on epochs (made on first use)
     // common device buffers
     int32_t *d_actions_in = nullptr;       // staging for xwb_step_host

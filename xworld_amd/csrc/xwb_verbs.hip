@@ -902,6 +902,39 @@ int xwb_xw_expert(xwb_sim *s, int32_t *actions_dev, int32_t *dist_dev, uint16_t 
     return XWB_OK;
 }
 
+int xwb_xw_symbolic_dims(const xwb_sim *s, size_t *planes, size_t *rows, size_t *cols) {
+    if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
+    if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_ARG, "not an xworld batch");
+    const size_t edge = (size_t)(s->cfg.visible_radius ? s->cfg.visible_radius : s->cfg.max_dim);
+    if (planes) *planes = XWB_SYM_PLANES;
+    if (rows) *rows = edge;
+    if (cols) *cols = edge;
+    return XWB_OK;
+}
+
+int xwb_xw_symbolic(xwb_sim *s, int16_t *out_dev, size_t out_bytes, void *stream) {
+    if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
+    XWB_ON_DEVICE(s);
+    XWB_LIVE(s);
+    if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_ARG, "not an xworld batch");
+    size_t edge = 0;
+    XWB_TRY(xwb_xw_symbolic_dims(s, nullptr, &edge, nullptr));
+    if (edge > (size_t)XW_MAX_DIM) return fail(XWB_ERR_ARG, "the frame has more squares than the kernel's tables");
+    if (!out_dev || out_bytes / (XWB_SYM_PLANES * edge * edge * sizeof(int16_t)) < (size_t)s->n)
+        return fail(XWB_ERR_ARG, "the output buffer is smaller than num_envs observations");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 1u) return fail(XWB_ERR_ARG, "the output buffer must be 2-byte aligned");
+    hipStream_t st = as_stream(stream);
+    // The frame xwb_xw_render_view describes, by its rules: ordered on `st`, the selection of xwb_xw_pack_grids under full
+    // observation (s->frame_src), the live state in egocentric mode.
+    HIP_TRY(launch_xw_symbolic(xw_params(s), s->frame_src, out_dev, st));
+    if (s->cfg.visible_radius) {
+        // as xwb_xw_render_view: a later xwb_reset_done regenerates finished envs on the internal queue -- not beside this kernel
+        HIP_TRY(hipEventRecord(s->ev_view, st));
+        HIP_TRY(hipStreamWaitEvent(s->side, s->ev_view, 0));
+    }
+    return XWB_OK;
+}
+
 int xwb_profile_begin(xwb_sim *s) {
     if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
     s->profiling = true;
