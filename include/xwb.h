@@ -404,7 +404,8 @@ int xwb_race_set_car(xwb_sim *sim, int32_t env, float x, float y, float angle);
 /* xworld: the strings behind the palette's name ids -- goal_names[id] for xwb_config.icon_name of goal icons, and per icon its
  * name and its colour ("na": none; properties.txt).  With them the library builds the teacher's sentences itself
  * (xworld_amd/csrc/xwb_language.h: the reference's per-task context-free grammars, python/context_free_grammar.py and the
- * tasks' _define_grammar, expanded with xwb-rng-v1 stream 3); the strings are copied. */
+ * tasks' _define_grammar, compiled here into the tables of xwb_sentence_ids.h and expanded with xwb-rng-v1 stream 3);
+ * the strings are copied. */
 int xwb_set_names(xwb_sim *sim, const char *const *goal_names, int32_t n_goal_names, const char *const *icon_names,
                   const char *const *icon_colors, int32_t n_icons);
 /* The teacher's sentence of one env after the last call, NUL-terminated ("" where the reference's get_state() shows "-").
@@ -414,7 +415,8 @@ int xwb_sentence(xwb_sim *sim, int32_t env, void *stream, char *out, size_t cap,
 /* The sentence functions behind xwb_sentence, callable without a batch or a GPU (host only; tests pin them to
  * xworld_amd/language.py, which is pinned to the reference's CFG): a 3-D task's sentence from its state (stage, event as in
  * xwb_env_state; name ids into goal_names, 0xffff none; direction 1 front, 2 behind, 3 left, 4 right), and a 2-D-native
- * task's instruction (task 5 / 7; timeup != 0: its "Time up ." message).  NUL-terminated; *need = bytes needed. */
+ * task's instruction (task 5 / 7; timeup != 0: its "Time up ." message).  NUL-terminated; *need = bytes needed.  A bound
+ * name or colour that holds white space is not one word -> XWB_ERR_ARG. */
 int xwb_language_sentence(int32_t task, int32_t stage, int32_t event, const char *const *goal_names, int32_t n_goal_names,
                           uint32_t name_a, uint32_t name_b, int32_t direction, uint32_t seed, uint32_t gid, uint32_t episode,
                           char *out, size_t cap, size_t *need);
@@ -442,7 +444,7 @@ int xwb_sentence_max_words(xwb_sim *sim, int32_t *n);
  * Needs xwb_set_names and xwb_set_vocabulary (else XWB_ERR_STATE); max_len >= 1. */
 int xwb_sentence_ids(xwb_sim *sim, int32_t *ids_dev, int32_t *len_dev, int32_t max_len, int32_t pad_id, int32_t silent_id,
                      void *stream);
-/* The same expansion on the host, without a batch or a GPU (the twin of xwb_language_sentence / _2d for tests): the word ids
+/* The same expansion on the host, without a batch or a GPU (what xwb_language_sentence / _2d join into a string): the word ids
  * of one sentence under a vocabulary.  Tasks 0-4 (and 6, 8: silent) take xwb_language_sentence's arguments; tasks 5 / 7 take
  * xwb_language_sentence_2d's -- the target's name is goal_names[name_a], its colour `color` (task 7), num_steps the step count,
  * event == 3 selects the "Time up ." message; stage, name_b and direction are unused.  Writes min(*need, cap) ids; *need = the

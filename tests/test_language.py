@@ -87,3 +87,101 @@ def test_library_sentences_equal_language_py():
         name, color = rng.choice(names), rng.choice(["red", "green", "blue", "yellow"])
         assert c2(task, 0, name, color, seed, gid, ep, steps) == language.sentence_2d(task, name, color, seed, gid, ep, steps) != ""
     assert c2(5, 1, "", "", 0, 0, 0, 0) == language.sentence_2d_timeup(5) == "Time up ."
+
+
+def _c_string(call):
+    """a string hook's two-call protocol (size, then bytes) -> (rc, text)"""
+    import ctypes as C
+    need = C.c_size_t()
+    rc = call(None, 0, C.byref(need))
+    if rc:
+        return rc, None
+    buf = C.create_string_buffer(need.value)
+    rc = call(buf, need.value, C.byref(need))
+    return rc, buf.value.decode()
+
+
+def test_2d_tasks_have_no_correct_or_wrong_message():
+    """The 2-D-native grammars have no `correct` / `wrong` rule: asked for one through the 3-D hook, the teacher is silent."""
+    import ctypes as C
+    from xworld_amd import lib
+    L = lib.load()
+    arr = (C.c_char_p * 2)(b"apple", b"fig")
+    for task in (5, 7):
+        for stage in (0, 1, 2):
+            for event in (1, 2):
+                for a in (0, 0xFFFF):
+                    rc, text = _c_string(lambda out, cap, need: L.xwb_language_sentence(task, stage, event, arr, 2, a, 0xFFFF, 0, 1, 2, 3,
+                                                                                        out, cap, need))
+                    assert rc == 0 and text == "", (task, stage, event, a)
+        rc, text = _c_string(lambda out, cap, need: L.xwb_language_sentence(task, 0, 3, arr, 2, 0xFFFF, 0xFFFF, 0, 1, 2, 3, out, cap, need))
+        assert rc == 0 and text == "Time up ."
+
+
+def test_a_bound_name_with_white_space_is_an_argument_error():
+    import ctypes as C
+    from xworld_amd import lib
+    L = lib.load()
+    XWB_ERR_ARG = -1                                       # include/xwb.h
+    for bad in (b"green apple", b"green\tapple", b"apple "):
+        arr = (C.c_char_p * 2)(bad, b"fig")
+        for task, a, b in ((0, 0, 0xFFFF), (1, 0, 0xFFFF), (2, 1, 0), (3, 0, 0xFFFF), (4, 0, 0xFFFF)):
+            rc, _ = _c_string(lambda out, cap, need: L.xwb_language_sentence(task, 1, 0, arr, 2, a, b, 1, 1, 2, 3, out, cap, need))
+            assert rc == XWB_ERR_ARG, (bad, task)
+            assert "a name or colour is not one word" in L.xwb_last_error().decode()
+        # the other name still makes a sentence, and the messages that bind no name are not affected
+        rc, text = _c_string(lambda out, cap, need: L.xwb_language_sentence(0, 1, 0, arr, 2, 1, 0xFFFF, 0, 1, 2, 3, out, cap, need))
+        assert rc == 0 and "fig" in text.split()
+        rc, text = _c_string(lambda out, cap, need: L.xwb_language_sentence(0, 2, 1, arr, 2, 0, 0xFFFF, 0, 1, 2, 3, out, cap, need))
+        assert rc == 0 and text == "Well done !"
+        for task, name, color in ((5, bad, b"na"), (7, bad, b"red"), (7, b"fig", bad)):
+            rc, _ = _c_string(lambda out, cap, need: L.xwb_language_sentence_2d(task, 0, name, color, 1, 2, 3, 4, out, cap, need))
+            assert rc == XWB_ERR_ARG, (bad, task)
+        rc, text = _c_string(lambda out, cap, need: L.xwb_language_sentence_2d(5, 1, bad, b"", 1, 2, 3, 4, out, cap, need))
+        assert rc == 0 and text == "Time up ."
+
+
+def test_strings_are_the_word_ids_looked_up():
+    """xwb_language_sentence / _2d against xwb_language_sentence_ids under a vocabulary that holds every word, exact case: the
+    ids mapped back through it are the string's words."""
+    import ctypes as C
+    import random
+    from xworld_amd import language, lib
+    L = lib.load()
+    names = ["apple", "avocado", "banana", "blueberry", "cabbage", "cauliflower", "cherry", "coconut", "cucumber", "fig"]
+    colors = ["red", "green", "blue", "yellow", "na"]
+    words = set(names + colors)
+    for g in language.GRAMMARS.values():
+        for alts in g.rules.values():
+            for alt in alts:
+                words.update(s[1:-1] for s in alt if s.startswith("'"))
+    vocab = ["<unk>"] + sorted(words)
+    arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
+    warr = (C.c_char_p * len(vocab))(*[w.encode() for w in vocab])
+    rng = random.Random(99)
+    spoke = 0
+    for i in range(600):
+        task = rng.choice((0, 1, 2, 3, 4, 5, 6, 7))
+        two_d = task in (5, 7)
+        stage, event = rng.choice(((1, 0), (1, 0), (1, 0), (2, 0), (2, 1), (2, 2), (2, 3)))
+        if two_d:
+            stage, event = rng.choice(((1, 0), (1, 0), (0, 3)))
+        seed, gid, ep, steps = rng.getrandbits(32), rng.getrandbits(32), rng.getrandbits(32), rng.randrange(1 << 16)
+        a, b, direction = rng.randrange(len(names)), rng.randrange(len(names)), rng.randint(1, 4)
+        color = rng.choice(colors).encode()
+        if two_d:
+            rc, text = _c_string(lambda out, cap, need: L.xwb_language_sentence_2d(task, int(event == 3), names[a].encode(), color, seed, gid,
+                                                                                   ep, steps, out, cap, need))
+        else:
+            rc, text = _c_string(lambda out, cap, need: L.xwb_language_sentence(task, stage, event, arr, len(names), a, b, direction, seed,
+                                                                                gid, ep, out, cap, need))
+        assert rc == 0
+        need = C.c_int32()
+        buf = (C.c_int32 * 64)()
+        lib.check(L.xwb_language_sentence_ids(task, stage, event, arr, len(names), a, b, direction, color, seed, gid, ep, steps, warr,
+                                              len(vocab), 0, 0, buf, 64, C.byref(need)))
+        ids = list(buf[:need.value])
+        assert 0 not in ids
+        assert " ".join(vocab[k] for k in ids) == text, (i, task, stage, event)
+        spoke += bool(text)
+    assert spoke >= 300

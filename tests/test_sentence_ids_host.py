@@ -1,5 +1,5 @@
-"""xwb_language_sentence_ids -- the host twin of the device kernel behind BatchedSimulator.sentence_ids (the same grammar tables,
-the same expansion code) -- against xworld_amd/language.py tokenised through a vocabulary.  language.py is pinned to the
+"""xwb_language_sentence_ids -- the host run of the walk behind BatchedSimulator.sentence_ids (the same grammar tables,
+the same expansion code as the device kernel) -- against xworld_amd/language.py tokenised through a vocabulary.  language.py is pinned to the
 reference's CFG by tests/golden/sentences.json (test_language.py).  CPU only.
 
 The vocabularies are the reference's dict files (tests/golden/nav_2d.txt, nav_3d.txt: byte-for-byte copies; they lack the shape

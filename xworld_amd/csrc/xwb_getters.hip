@@ -453,48 +453,42 @@ int xwb_get_extra_info(xwb_sim *s, int32_t env, void *stream, char *out, size_t 
     return XWB_OK;
 }
 
-// BatchedSimulator.sentence / _group_sentence (xworld_amd/batched.py), on this side of the ABI
-static int group_sentence(xwb_sim *s, int32_t env, void *stream, const xwb_env_state &st, int task, int stage, int event, int target,
-                          int steps_in_task, std::string *out) {
-    out->clear();
-    const uint32_t gid = s->cfg.env_gid0 + (uint32_t)env;
-    if (task == 5 || task == 7) {
-        // 2-D-native Target / ColorTarget: they speak on the teach() call that picked the target, and "Time up ." on the
-        // one_channel step that runs out of time (xworld_task.py:205-211): back to idle with the target still recorded
-        if (stage == 0 && event == 0 && target >= 0 && st.num_steps > 0 && s->cfg.task_mode == XWB_TASKMODE_ONE_CHANNEL) {
-            *out = xwb::lang::sentence_2d_timeup(task);
-            return XWB_OK;
-        }
-        if (stage != 1 || steps_in_task != 0 || target < 0) return XWB_OK;
-        uint16_t code = 0;
-        const int cells = s->cfg.max_dim * s->cfg.max_dim;
-        if (target >= cells) return XWB_OK;
-        HIP_TRY(hipMemcpyAsync(&code, s->d_grid + (size_t)env * cells + target, 2, hipMemcpyDeviceToHost, as_stream(stream)));
-        HIP_TRY(hipStreamSynchronize(as_stream(stream)));
-        const int icon = (int)(code & 0x7fffu) - 1;           // (xw_device.h CELL_ICON_MASK: bit 15 marks target goals)
-        if (icon < 0 || icon >= (int)s->icon_names.size()) return XWB_OK;   // (two groups: the 3-D stage may have moved the goal away since)
-        *out = xwb::lang::sentence_2d(task, s->icon_names[icon], s->icon_colors[icon], s->cfg.seed, gid, st.episode, (uint32_t)st.num_steps);
-        return XWB_OK;
-    }
-    const uint32_t sn = st.xw_sentence_names;
-    *out = xwb::lang::sentence(task, stage, event, s->goal_names, sn & 0xffffu, sn >> 16, task == 3 && target >= 0 ? (target >> 8) & 7 : 0,
-                               s->cfg.seed, gid, st.episode);
-    return XWB_OK;
-}
-
+// BatchedSimulator.sentence (xworld_amd/batched.py) on this side of the ABI: the selection and the walk of xwb_sentence_ids.h
+// over the host tables of xwb_set_names, the ids looked up in their word list
 static int env_sentence(xwb_sim *s, int32_t env, void *stream, std::string *out) {
+    out->clear();
     xwb_env_state st;
-    int rc = xwb_get_env_state(s, env, stream, &st);
-    if (rc) return rc;
-    if (st.xw_group_ran == 1)      // exclusive scheduling: only the group the last teach() ran can have spoken
-        return group_sentence(s, env, stream, st, st.xw_task2, st.xw_stage2, st.xw_event2, st.xw_target2, st.xw_steps_in_task2, out);
-    rc = group_sentence(s, env, stream, st, st.xw_task, st.xw_stage, st.xw_event, st.xw_target, st.xw_steps_in_task, out);
-    if (rc || st.xw_group_ran == 0) return rc;
-    // two task groups run side by side: the first one (conf order) that speaks wins -- Task::teacher_speak only records into
-    // an empty buffer (teaching_task.cpp:118-127)
-    if (out->empty() && s->cfg.n_tasks2 > 0)
-        rc = group_sentence(s, env, stream, st, st.xw_task2, st.xw_stage2, st.xw_event2, st.xw_target2, st.xw_steps_in_task2, out);
-    return rc;
+    XWB_TRY(xwb_get_env_state(s, env, stream, &st));
+    auto packed = [](int task, int stage, int event, int target) { return task << 24 | event << 20 | stage << 16 | (target & 0xffff); };
+    xwb::sent::EnvWords w;
+    w.task_state = packed(st.xw_task, st.xw_stage, st.xw_event, st.xw_target); w.task_steps = st.xw_steps_in_task;
+    w.two = s->d_task_state2 != nullptr;
+    w.task_state2 = packed(st.xw_task2, st.xw_stage2, st.xw_event2, st.xw_target2); w.task_steps2 = st.xw_steps_in_task2;
+    w.num_steps = (int32_t)st.num_steps;
+    w.sent_names = st.xw_sentence_names;
+    w.grp_order = st.xw_group_ran < 0 ? -1 : st.xw_group_first | st.xw_group_ran << 1;
+    w.one_channel = s->cfg.task_mode == XWB_TASKMODE_ONE_CHANNEL;
+    w.cells = s->cfg.max_dim * s->cfg.max_dim;
+    int rc = XWB_OK;
+    auto cell = [&](int c) {                                  // one two-byte copy, and only when pick_env asks
+        uint16_t code = 0;
+        rc = [&]() -> int {
+            HIP_TRY(hipMemcpyAsync(&code, s->d_grid + (size_t)env * w.cells + c, 2, hipMemcpyDeviceToHost, as_stream(stream)));
+            HIP_TRY(hipStreamSynchronize(as_stream(stream)));
+            return XWB_OK;
+        }();
+        return code;
+    };
+    xwb::sent::Slots b;
+    bool first = false, is2d = false;
+    const bool speaks = xwb::sent::pick_env(s->sent_host_lay, w, cell, b, first, is2d);
+    if (rc || !speaks) return rc;
+    std::vector<int32_t> ids;
+    if (!xwb::lang::host_walk(s->sent_host_lay, b, first, s->cfg.seed, s->cfg.env_gid0 + (uint32_t)env, st.episode,
+                              is2d ? 4u * (uint32_t)st.num_steps : 0u, ids))
+        return fail(XWB_ERR_ARG, "sentence expansion out of range");
+    const std::string err = xwb::lang::join_words(s->sent_words, ids, *out);
+    return err.empty() ? XWB_OK : fail(XWB_ERR_ARG, err);
 }
 
 int xwb_set_names(xwb_sim *s, const char *const *goal_names, int32_t n_goal_names, const char *const *icon_names,
@@ -511,8 +505,23 @@ int xwb_set_names(xwb_sim *s, const char *const *goal_names, int32_t n_goal_name
     s->goal_names.assign(goal_names, goal_names + n_goal_names);
     s->icon_names.assign(icon_names, icon_names + n_icons);
     s->icon_colors.assign(icon_colors, icon_colors + n_icons);
+    // the tables behind xwb_sentence and the state packets, once per batch: every word interned, host only
+    xwb::lang::Vocab v(true);
+    xwb::lang::SentLayout L;
+    const std::string err = xwb::lang::compile_sentence_tables(v, s->goal_names, s->icon_names, s->icon_colors, L);
+    if (!err.empty()) return fail(XWB_ERR_ARG, err);
+    s->sent_host_tab.swap(L.tab);
+    s->sent_words.swap(v.words);
+    s->sent_host_lay = L.lay;
+    s->sent_host_lay.t = s->sent_host_tab.data();
     s->have_names = true;
     if (s->have_vocab) return sentence_tables_rebuild(s);     // the word ids of the bound names (xwb_sentence_ids)
+    return XWB_OK;
+}
+
+static int copy_out(const std::string &str, char *out, size_t cap, size_t *need) {
+    *need = str.size() + 1;
+    if (out && cap >= str.size() + 1) memcpy(out, str.c_str(), str.size() + 1);
     return XWB_OK;
 }
 
@@ -523,34 +532,37 @@ int xwb_sentence(xwb_sim *s, int32_t env, void *stream, char *out, size_t cap, s
     if (env < 0 || env >= s->n) return fail(XWB_ERR_ARG, "env out of range");
     XWB_ON_DEVICE(s);
     std::string str;
-    const int rc = env_sentence(s, env, stream, &str);
-    if (rc) return rc;
-    *need = str.size() + 1;
-    if (out && cap >= str.size() + 1) memcpy(out, str.c_str(), str.size() + 1);
-    return XWB_OK;
+    XWB_TRY(env_sentence(s, env, stream, &str));
+    return copy_out(str, out, cap, need);
 }
 
-static int copy_out(const std::string &str, char *out, size_t cap, size_t *need) {
-    *need = str.size() + 1;
-    if (out && cap >= str.size() + 1) memcpy(out, str.c_str(), str.size() + 1);
-    return XWB_OK;
+// a stateless hook's sentence as a string: the ids of an interning vocabulary, joined
+static int hook_string(bool two_d, int32_t task, int32_t stage, int32_t event, const char *const *goal_names, int32_t n_goal_names,
+                       uint32_t name_a, uint32_t name_b, int32_t direction, const char *color, uint32_t seed, uint32_t gid,
+                       uint32_t episode, uint32_t num_steps, char *out, size_t cap, size_t *need) {
+    if (!need) return fail(XWB_ERR_ARG, "NULL argument");
+    xwb::lang::Vocab v(true);
+    std::vector<int32_t> ids;
+    std::string str, err = xwb::lang::hook_sentence(v, two_d, task, stage, event, goal_names, n_goal_names, name_a, name_b, direction, color,
+                                                    seed, gid, episode, num_steps, ids);
+    if (err.empty()) err = xwb::lang::join_words(v.words, ids, str);
+    return err.empty() ? copy_out(str, out, cap, need) : fail(XWB_ERR_ARG, err);
 }
 
 int xwb_language_sentence(int32_t task, int32_t stage, int32_t event, const char *const *goal_names, int32_t n_goal_names,
                           uint32_t name_a, uint32_t name_b, int32_t direction, uint32_t seed, uint32_t gid, uint32_t episode,
                           char *out, size_t cap, size_t *need) {
-    if (!need || (n_goal_names > 0 && !goal_names) || n_goal_names < 0) return fail(XWB_ERR_ARG, "NULL argument");
-    std::vector<std::string> names;
-    for (int i = 0; i < n_goal_names; ++i) { if (!goal_names[i]) return fail(XWB_ERR_ARG, "NULL name"); names.push_back(goal_names[i]); }
-    return copy_out(xwb::lang::sentence(task, stage, event, names, name_a, name_b, direction, seed, gid, episode), out, cap, need);
+    // (task 7's instruction binds a colour, which only xwb_language_sentence_2d carries: here it has its time-up message alone)
+    if (task == 7 && event != 3) stage = 0;
+    return hook_string(false, task, stage, event, goal_names, n_goal_names, name_a, name_b, direction, nullptr, seed, gid, episode, 0,
+                       out, cap, need);
 }
 
 int xwb_language_sentence_2d(int32_t task, int32_t timeup, const char *goal_name, const char *color, uint32_t seed, uint32_t gid,
                              uint32_t episode, uint32_t num_steps, char *out, size_t cap, size_t *need) {
-    if (!need) return fail(XWB_ERR_ARG, "NULL argument");
-    if (timeup) return copy_out(xwb::lang::sentence_2d_timeup(task), out, cap, need);
-    if (!goal_name || !color) return fail(XWB_ERR_ARG, "NULL argument");
-    return copy_out(xwb::lang::sentence_2d(task, goal_name, color, seed, gid, episode, num_steps), out, cap, need);
+    if (!timeup && (!goal_name || !color)) return fail(XWB_ERR_ARG, "NULL argument");
+    return hook_string(true, task, 1, timeup ? 3 : 0, &goal_name, timeup ? 0 : 1, 0, 0xFFFFu, 0, color, seed, gid, episode, num_steps,
+                       out, cap, need);
 }
 
 int xwb_get_state_packet(xwb_sim *s, int32_t env, float reward, void *stream, uint8_t *out_host, size_t cap,

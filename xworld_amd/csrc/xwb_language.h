@@ -1,4 +1,4 @@
-// xworld_amd/csrc/xwb_language.h -- the teacher's sentences of XWorld2D, host side (the C ABI's copy of xworld_amd/language.py).
+// xworld_amd/csrc/xwb_language.h -- the teacher's sentences of XWorld2D, host side (the C ABI's copy of xworld_amd/language.py's rule texts).
 //
 // In the reference every task owns a context-free grammar (python/context_free_grammar.py; games/xworld3d/tasks/
 // XWorld3DNav*.py and games/xworld/tasks/XWorldNav*.py: `_define_grammar`); its idle stage binds the start symbol and the
@@ -6,8 +6,11 @@
 // sentence of an env is a pure function of the batch state (task, bound goal names, direction word, stage, event,
 // episode) and of xwb-rng-v1 stream 3 ("language": key = (seed, global env id), counter = (block, episode, 3, 0); one
 // below(n) per expanded non-terminal, also when it is bound), so nothing is stored per env and the device never sees
-// strings.  The rule texts, the stream and the order of the draws are those of language.py; tests/test_gpu_language_c.py
-// compares the two sentence for sentence, and language.py is pinned to the reference's CFG by tests/golden/sentences.json.
+// strings.  This file holds the rule texts, their compiler into xwb_sentence_ids.h's flat tables and the host's draw; the
+// walk itself is xwb_sentence_ids.h's, for strings as for word ids: a string is the id sequence of an interning vocabulary
+// looked up in its word list.  The rule texts, the stream and the order of the draws are those of language.py;
+// tests/test_language.py and tests/test_sentence_ids_host.py compare the two sentence for sentence, and language.py is pinned
+// to the reference's CFG by tests/golden/sentences.json.
 #pragma once
 #include "xwb_sentence_ids.h"
 
@@ -50,8 +53,6 @@ struct Stream {
     }
 };
 
-typedef std::map<std::string, std::string> Bindings;
-
 inline std::vector<std::string> split_ws(const std::string &s) {
     std::vector<std::string> out;
     std::istringstream is(s);
@@ -60,8 +61,7 @@ inline std::vector<std::string> split_ws(const std::string &s) {
     return out;
 }
 
-// Rules `X -> a b | 'c' d` (terminals in single quotes).  expand() = CFG.generate(): left-most derivation, one choice per
-// non-terminal; a binding narrows a rule to one alternative.
+// Rules `X -> a b | 'c' d` (terminals in single quotes), parsed for compile_sentence_tables
 struct Grammar {
     std::map<std::string, std::vector<std::vector<std::string>>> rules;
     explicit Grammar(const std::string &text) {
@@ -84,29 +84,7 @@ struct Grammar {
             rules[lhs[0]] = alts;
         }
     }
-    template <typename Choose>
-    void gen(const std::string &sym, Choose &choose, const Bindings &b, std::vector<std::string> &out) const {
-        if (sym[0] == '\'') { out.push_back(sym.substr(1, sym.size() - 2)); return; }
-        const Bindings::const_iterator it = b.find(sym);
-        std::vector<std::vector<std::string>> bound;
-        const std::vector<std::vector<std::string>> *alts;
-        if (it != b.end()) { bound.push_back(split_ws(it->second)); alts = &bound; }
-        else alts = &rules.at(sym);
-        const std::vector<std::string> alt = (*alts)[choose((uint32_t)alts->size())];
-        for (size_t i = 0; i < alt.size(); ++i) gen(alt[i], choose, b, out);
-    }
-    template <typename Choose>
-    std::string expand(Choose &choose, const Bindings &b) const {
-        std::vector<std::string> words;
-        gen("S", choose, b, words);
-        std::string s;
-        for (size_t i = 0; i < words.size(); ++i) { if (i) s += ' '; s += words[i]; }
-        return s;
-    }
 };
-
-struct First { uint32_t operator()(uint32_t) { return 0; } };
-struct Draw { Stream &st; uint32_t operator()(uint32_t n) { return st.below(n); } };
 
 // task id (include/xwb.h XWB_TASK_*) -> grammar; nullptr: the task never speaks
 inline const Grammar *grammar_of(int task) {
@@ -207,78 +185,27 @@ inline const Grammar *grammar_of(int task) {
     }
 }
 
-inline std::string quoted(const std::string &name) { return "'" + name + "'"; }
-
-// language.sentence(): a 3-D task's sentence after the last call ("" where the reference's get_state() shows "-").
-// stage / event as in xwb_env_state (1 = navigation; 1 correct, 2 wrong, 3 time-up); name_a / name_b = goal-name ids bound
-// at the idle stage (0xffff: none); direction: xw_device.h DIR_* (1 front, 2 behind, 3 left, 4 right)
-inline std::string sentence(int task, int stage, int event, const std::vector<std::string> &goal_names, uint32_t name_a, uint32_t name_b,
-                            int direction, uint32_t seed, uint32_t gid, uint32_t episode) {
-    const Grammar *g = grammar_of(task);
-    if (!g) return "";
-    static const char *const event_rule[4] = {nullptr, "correct", "wrong", "timeup"};
-    if (event >= 1 && event <= 3) {
-        First f;
-        Bindings b;
-        b["S"] = event_rule[event];
-        return g->expand(f, b);
-    }
-    if (stage != 1 || name_a == 0xFFFFu || name_a >= goal_names.size()) return "";
-    Stream st(seed, gid, episode, 3);
-    Draw d{st};
-    Bindings b;
-    b["S"] = "start";
-    if (task == 2) {
-        if (name_b >= goal_names.size()) return "";
-        b["G1"] = quoted(goal_names[name_a]); b["G2"] = quoted(goal_names[name_b]);
-    } else {
-        b["G"] = quoted(goal_names[name_a]);
-    }
-    if (task == 3) {
-        static const char *const words[5] = {"", "FRONT", "BEHIND", "LEFT", "RIGHT"};
-        if (direction < 1 || direction > 4) return "";
-        b["P"] = words[direction];
-    }
-    return g->expand(d, b);
-}
-
-// language.sentence_2d(): the instruction of a 2-D-native task on the teach() call that picked its target
-inline std::string sentence_2d(int task, const std::string &goal_name, const std::string &color, uint32_t seed, uint32_t gid,
-                               uint32_t episode, uint32_t num_steps) {
-    const Grammar *g = grammar_of(task);
-    if (!g) return "";
-    Stream st(seed, gid, episode, 3);
-    st.blk = 4 * num_steps;
-    Draw d{st};
-    Bindings b;
-    b["S"] = "start";
-    if (task == 7) { b["O"] = quoted(goal_name); b["C"] = quoted(color); }
-    else b["G"] = quoted(goal_name);
-    return g->expand(d, b);
-}
-
-inline std::string sentence_2d_timeup(int task) {
-    const Grammar *g = grammar_of(task);
-    if (!g) return "";
-    First f;
-    Bindings b;
-    b["S"] = "timeup";
-    return g->expand(f, b);
-}
-
-// ---- word ids (xwb_set_vocabulary / xwb_sentence_ids): the rule texts above compiled into xwb_sentence_ids.h's flat tables ----
+// ---- the rule texts above compiled into xwb_sentence_ids.h's flat tables, under a vocabulary ----
 
 inline std::string fold_ascii(std::string w) {
     for (char &ch : w) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch - 'A' + 'a');
     return w;
 }
 
-// words[i] -> i.  Empty entries (blank lines of a dict file) keep their ids and never match a word.
+// words[i] -> i.  Empty entries (blank lines of a dict file) keep their ids and never match a word.  intern: the vocabulary
+// behind the strings instead -- an unknown word is appended as it stands (no folding, no unk) and words[id] gives it back.
 struct Vocab {
     std::map<std::string, int32_t> ids;
+    std::vector<std::string> words;             // intern only
     int32_t unk = 0;
-    bool fold = false;
-    int32_t id(const std::string &w) const {
+    bool fold = false, intern = false;
+    explicit Vocab(bool interning = false) : intern(interning) {}
+    int32_t id(const std::string &w) {
+        if (intern) {
+            const auto r = ids.emplace(w, (int32_t)words.size());
+            if (r.second) words.push_back(w);
+            return r.first->second;
+        }
         const std::map<std::string, int32_t>::const_iterator it = ids.find(fold ? fold_ascii(w) : w);
         return it == ids.end() ? unk : it->second;
     }
@@ -301,11 +228,14 @@ inline std::string make_vocab(const char *const *words, int32_t n_words, int32_t
     return "";
 }
 
+inline bool has_space(const std::string &s) {
+    for (char ch : s) if (ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\v' || ch == '\f') return true;
+    return false;
+}
 // the word id of a bound name / colour: the whole string is one word
-inline bool one_word(const std::string &s) {
-    if (s.empty()) return false;
-    for (char ch : s) if (ch == ' ' || ch == '\t' || ch == '\n' || ch == '\r' || ch == '\v' || ch == '\f') return false;
-    return true;
+inline bool one_word(const std::string &s) { return !s.empty() && !has_space(s); }
+inline std::string not_one_word(const std::string &s) {
+    return "a name or colour is not one word: '" + s + "' (a bound name is one vocabulary entry)";
 }
 
 struct SentLayout {
@@ -326,13 +256,14 @@ inline int slot_of(int task, const std::string &sym) {
     return -1;
 }
 
-// Builds the tables of every task with a grammar.  "" on success, else what is wrong.
-inline std::string compile_sentence_tables(const Vocab &v, const std::vector<std::string> &goal_names, const std::vector<std::string> &icon_names,
+// Builds the tables of every task with a grammar.  "" on success, else what is wrong.  (An interning vocabulary takes the
+// names as they stand: sentence_text refuses the one a sentence binds.)
+inline std::string compile_sentence_tables(Vocab &v, const std::vector<std::string> &goal_names, const std::vector<std::string> &icon_names,
                                            const std::vector<std::string> &icon_colors, SentLayout &out) {
     using namespace sent;
     for (const std::vector<std::string> *names : {&goal_names, &icon_names, &icon_colors})
         for (const std::string &s : *names)
-            if (!one_word(s)) return "a name or colour is not one word: '" + s + "' (a bound name is one vocabulary entry)";
+            if (!v.intern && !one_word(s)) return not_one_word(s);
     std::vector<int32_t> special(N_TASKS * N_SPECIAL, -1), nts, alts, syms;   // nts / alts: pairs (first, count)
     std::vector<int32_t> nt_task;                                             // owning task of each non-terminal
     static const char *const SPECIAL_NAMES[N_SPECIAL] = {"start", "correct", "wrong", "timeup", "finish", "FRONT", "BEHIND", "LEFT", "RIGHT"};
@@ -445,6 +376,63 @@ inline int32_t max_sentence_words(int task) {
         return l;
     }();
     return task >= 0 && task < sent::N_TASKS ? layout.max_words[task] : 0;
+}
+
+// ---- one sentence on the host: the slots sent::pick_* selected, walked through the tables ----
+
+// The ids of the sentence; blk0: the first block of stream 3 it draws from (a 2-D-native task: 4 * num_steps).  false: the
+// tables or the stack are out of range.
+inline bool host_walk(const sent::SentTab &T, const sent::Slots &b, bool first, uint32_t seed, uint32_t gid, uint32_t episode,
+                      uint32_t blk0, std::vector<int32_t> &ids) {
+    Stream st(seed, gid, episode, 3);
+    st.blk = blk0;
+    auto draw = [&](uint32_t n) { return first ? 0u : st.below(n); };
+    auto emit = [&](int32_t, int32_t w) { ids.push_back(w); };
+    int32_t stack[sent::STACK_MAX];
+    return sent::expand(T, b, draw, stack, 1, emit) >= 0;
+}
+
+// ids of an interning vocabulary -> "w0 w1 ...".  "" on success.  No word of the rule texts holds white space, so one that
+// does is a bound name that is not one word.
+inline std::string join_words(const std::vector<std::string> &words, const std::vector<int32_t> &ids, std::string &out) {
+    out.clear();
+    for (size_t i = 0; i < ids.size(); ++i) {
+        const std::string &w = words[ids[i]];
+        if (has_space(w)) return not_one_word(w);
+        if (i) out += ' ';
+        out += w;
+    }
+    return "";
+}
+
+// One sentence without a batch (the xwb_language_* hooks): the tables of these names under v, the slots, the walk.  two_d: a
+// 2-D-native task's arguments -- the target's icon is (goal_names[name_a], color), event 3 selects its time-up message, which
+// binds no name.  "" on success, else what is wrong; ids stays empty when the teacher is silent.
+inline std::string hook_sentence(Vocab &v, bool two_d, int task, int stage, int event, const char *const *goal_names, int32_t n_goals,
+                                 uint32_t name_a, uint32_t name_b, int direction, const char *color, uint32_t seed, uint32_t gid,
+                                 uint32_t episode, uint32_t num_steps, std::vector<int32_t> &ids) {
+    if (n_goals < 0 || (n_goals > 0 && !goal_names)) return "NULL argument";
+    std::vector<std::string> goals, inames, icolors;
+    for (int32_t i = 0; i < n_goals; ++i) {
+        if (!goal_names[i]) return "NULL name";
+        goals.push_back(goal_names[i]);
+    }
+    if (two_d && event != 3) {
+        if (name_a >= goals.size()) return "name_a out of range";
+        if (task == 7 && !color) return "NULL colour";
+        inames.push_back(goals[name_a]);
+        icolors.push_back(color ? color : "na");
+    }
+    SentLayout L;
+    const std::string err = compile_sentence_tables(v, goals, inames, icolors, L);
+    if (!err.empty()) return err;
+    L.lay.t = L.tab.data();
+    sent::Slots b;
+    bool first = false;
+    const bool speaks = two_d ? sent::pick_2d(L.lay, task, event == 3, 0, b, first)
+                              : sent::pick_3d(L.lay, task, stage, event, name_a, name_b, direction, b, first);
+    if (speaks && !host_walk(L.lay, b, first, seed, gid, episode, two_d ? 4 * num_steps : 0, ids)) return "sentence expansion out of range";
+    return "";
 }
 
 }  // namespace lang

@@ -1,5 +1,7 @@
-// xwb_sentence_ids.h -- the teacher's sentence as word ids: the flat grammar tables and the expansion that walks them, shared by
-// the device kernel (xwb_sentence_ids.hip: one lane per env) and its host twin (xwb_language_sentence_ids).
+// xwb_sentence_ids.h -- the teacher's sentence as word ids: the flat grammar tables, the rule for which task group spoke, the
+// slots it binds and the expansion that walks the tables.  The one path to a sentence, on the device (xwb_sentence_ids.hip: one
+// lane per env) and on the host (xwb_language.h host_walk: xwb_sentence, the state packets, the xwb_language_* hooks; a string
+// is the id sequence looked up in a word list).
 //
 // xwb_language.h's rule texts are compiled (compile_sentence_tables there) into one int32 table per batch:
 //   [task * N_SPECIAL + k]         per task 0..8: the non-terminal of start, correct, wrong, timeup, finish, FRONT, BEHIND, LEFT,
@@ -9,7 +11,8 @@
 //   [off_sym + i]                  a symbol: a word id (terminal), SYM_NT | non-terminal, SYM_SLOT | slot (a bound rule)
 //   [off_goal + name id]           word id of each goal name (xwb_set_names' goal_names)
 //   [off_iname / off_icolor + icon] word id of each icon's name / colour (the 2-D-native tasks bind those)
-// A bound rule (S, P, G, G1, G2, O, C) has one alternative and still consumes one below(n) draw, as in Grammar::gen.
+// A bound rule (S, P, G, G1, G2, O, C) has one alternative and still consumes one below(n) draw, as in language.py's
+// Grammar.expand.
 #pragma once
 #include <stdint.h>
 
@@ -41,7 +44,7 @@ struct Slots {
     int32_t start_nt = -1, p_nt = -1, g = 0, g1 = 0, g2 = 0, o = 0, c = 0;
 };
 
-// Grammar::gen as a loop: the stack holds the symbols still to expand, the left-most on top, so the draws come in the recursion's
+// language.py's Grammar.expand as a loop: the stack holds the symbols still to expand, the left-most on top, so the draws come in the recursion's
 // order.  emit(k, word) receives word k of the sentence.  Returns the word count, -1 when the tables or the stack are out of range.
 // stk: STACK_MAX entries, `stride` apart.
 template <typename Draw, typename Emit>
@@ -82,7 +85,7 @@ XWB_SENT_HD int32_t expand(const SentTab &T, const Slots &b, Draw &draw, int32_t
     return n;
 }
 
-// language.sentence() / xwb::lang::sentence: which rule S is bound to, and the names.  *first: the event messages take the
+// language.sentence(): which rule S is bound to, and the names.  *first: the event messages take the
 // first alternative everywhere and draw nothing.  Returns false when the teacher is silent.
 XWB_SENT_HD bool pick_3d(const SentTab &T, int task, int stage, int event, uint32_t name_a, uint32_t name_b, int direction, Slots &b,
                          bool &first) {
@@ -131,6 +134,53 @@ XWB_SENT_HD bool pick_2d(const SentTab &T, int task, bool timeup, int icon, Slot
     }
     b.start_nt = sp[SP_START];
     return b.start_nt >= 0;
+}
+
+// One env's packed state, as the step kernels leave it: task_state = target (int16) | stage << 16 | event << 20 | task << 24
+// (xwb_get_env_state unpacks the same bits), sent_names = name id a | b << 16
+struct EnvWords {
+    int32_t task_state, task_steps;
+    bool two;                                 // a second task group: its two words
+    int32_t task_state2, task_steps2;
+    int32_t num_steps;
+    uint32_t sent_names;
+    int grp_order;                            // exclusive scheduling of two groups: the grp_order byte (bit 1: the group that ran), else -1
+    bool one_channel;
+    int cells;
+};
+
+// What one task group says, from its packed task state (batched.py: BatchedSimulator's rule for one group).  cell_at(cell): the grid code there, read only for the
+// 2-D-native tasks' instruction.
+template <typename CellAt>
+XWB_SENT_HD bool pick_group(const SentTab &T, const EnvWords &w, int32_t ts, int32_t tsteps, CellAt &cell_at, Slots &b, bool &first,
+                            bool &is2d) {
+    const int task = (ts >> 24) & 0xf, stage = (ts >> 16) & 0xf, event = (ts >> 20) & 0xf;
+    const int target = (int16_t)(ts & 0xffff);
+    if (task == 5 || task == 7) {
+        // 2-D-native Target / ColorTarget: they speak on the teach() call that picked the target, and "Time up ." on the
+        // one_channel step that ran out of time (xworld_task.py:205-211): back to idle with the target still recorded
+        is2d = true;
+        if (stage == 0 && event == 0 && target >= 0 && w.num_steps > 0 && w.one_channel) return pick_2d(T, task, true, -1, b, first);
+        if (stage != 1 || tsteps != 0 || target < 0 || target >= w.cells) return false;
+        // (bit 15 marks target goals; two groups: the 3-D stage may have moved the goal away since, then no icon is there)
+        return pick_2d(T, task, false, (int)(cell_at(target) & 0x7fffu) - 1, b, first);
+    }
+    is2d = false;
+    const int direction = task == 3 && target >= 0 ? (target >> 8) & 7 : 0;
+    return pick_3d(T, task, stage, event, w.sent_names & 0xffffu, w.sent_names >> 16, direction, b, first);
+}
+
+// BatchedSimulator.sentence: does the teacher speak, and what -- the group the last teach() ran (exclusive scheduling), else
+// the first group in conf order that speaks: Task::teacher_speak only records into an empty buffer (teaching_task.cpp:118-127).
+// is2d: a 2-D-native task spoke, its draws start at block 4 * num_steps.
+template <typename CellAt>
+XWB_SENT_HD bool pick_env(const SentTab &T, const EnvWords &w, CellAt &cell_at, Slots &b, bool &first, bool &is2d) {
+    const int ran = w.grp_order < 0 ? -1 : (w.grp_order >> 1) & 1;
+    if (ran == 1) return w.two && pick_group(T, w, w.task_state2, w.task_steps2, cell_at, b, first, is2d);
+    if (pick_group(T, w, w.task_state, w.task_steps, cell_at, b, first, is2d)) return true;
+    if (ran == 0 || !w.two) return false;
+    b = Slots();
+    return pick_group(T, w, w.task_state2, w.task_steps2, cell_at, b, first, is2d);
 }
 
 }  // namespace sent

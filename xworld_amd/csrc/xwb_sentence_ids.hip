@@ -1,10 +1,10 @@
 // xwb_sentence_ids.hip -- the teacher's sentence of every env as word ids, in one launch (include/xwb.h xwb_set_vocabulary,
-// xwb_sentence_max_words, xwb_sentence_ids) and its host twin (xwb_language_sentence_ids).
+// xwb_sentence_max_words, xwb_sentence_ids), and the same walk for one sentence on the host (xwb_language_sentence_ids).
 //
 // The sentence of an env is a pure function of its live state and of xwb-rng-v1 stream 3 (xwb_language.h), so the device expands
-// it itself: one lane per env reads what xwb_get_env_state / env_sentence read (task FSMs, episode, step count, bound name ids,
-// the exclusive group order; for the 2-D-native tasks the one grid cell at the target), picks the group that spoke by
-// env_sentence's rules and walks the grammar tables (xwb_sentence_ids.h) with an explicit stack in LDS.  The launch is ordered
+// it itself: one lane per env reads the packed words xwb_get_env_state unpacks (task FSMs, episode, step count, bound name ids,
+// the exclusive group order; for the 2-D-native tasks the one grid cell at the target), picks the group that spoke
+// (xwb_sentence_ids.h pick_env, as xwb_sentence does) and walks the grammar tables with an explicit stack in LDS.  The launch is ordered
 // on the caller's stream only: it reads nothing the regeneration pass on the internal queue writes (that pass fills the
 // shadow arrays), exactly like the copies of xwb_get_env_state.
 #include "xwb_sim.h"
@@ -33,24 +33,10 @@ struct SentIdsParams {
     int32_t *ids, *len;
 };
 
-// BatchedSimulator._group_sentence / group_sentence (xwb_getters.hip) for one group's packed task state
-__device__ __forceinline__ bool group_pick(const SentIdsParams &p, const sent::SentTab &T, int e, int32_t ts, int32_t tsteps, int32_t nsteps,
-                                           sent::Slots &b, bool &first, bool &is2d) {
-    const int task = (ts >> 24) & 0xf, stage = (ts >> 16) & 0xf, event = (ts >> 20) & 0xf;
-    const int target = (int16_t)(ts & 0xffff);
-    if (task == 5 || task == 7) {
-        is2d = true;
-        // the one_channel step that ran out of time: back to idle with the target still recorded
-        if (stage == 0 && event == 0 && target >= 0 && nsteps > 0 && p.one_channel) return sent::pick_2d(T, task, true, -1, b, first);
-        if (stage != 1 || tsteps != 0 || target < 0 || target >= p.cells) return false;
-        const int icon = (int)(p.grid[(size_t)e * (size_t)p.cells + (size_t)target] & 0x7fffu) - 1;   // (bit 15: target goal)
-        return sent::pick_2d(T, task, false, icon, b, first);
-    }
-    is2d = false;
-    const uint32_t sn = p.sent_names[e];
-    const int direction = task == 3 && target >= 0 ? (target >> 8) & 7 : 0;
-    return sent::pick_3d(T, task, stage, event, sn & 0xffffu, sn >> 16, direction, b, first);
-}
+struct DevCell {                             // the grid code under a cell of env e
+    const uint16_t *grid;
+    __device__ __forceinline__ uint16_t operator()(int cell) const { return grid[cell]; }
+};
 
 struct DevDraw {
     Stream st;
@@ -77,27 +63,26 @@ __global__ __launch_bounds__(SENT_BLOCK) void xw_sentence_ids_kernel(SentIdsPara
     }
     const int e = blockIdx.x * SENT_BLOCK + threadIdx.x;
     if (e >= p.n) return;
-    const int32_t nsteps = p.num_steps[e];
-    const int ran = p.grp_order ? (p.grp_order[e] >> 1) & 1 : -1;
+    sent::EnvWords w;
+    w.task_state = p.task_state[e]; w.task_steps = p.task_steps[e];
+    w.two = p.task_state2 != nullptr;
+    w.task_state2 = w.two ? p.task_state2[e] : 0; w.task_steps2 = w.two ? p.task_steps2[e] : 0;
+    w.num_steps = p.num_steps[e];
+    w.sent_names = p.sent_names[e];
+    w.grp_order = p.grp_order ? (int)p.grp_order[e] : -1;
+    w.one_channel = p.one_channel != 0;
+    w.cells = p.cells;
+    DevCell cell{p.grid + (size_t)e * (size_t)p.cells};
     sent::Slots b;
-    bool first = false, is2d = false, speaks;
-    // env_sentence: the group the last teach() ran (exclusive scheduling), else the first group (conf order) that speaks --
-    // Task::teacher_speak only records into an empty buffer
-    if (ran == 1) speaks = p.task_state2 && group_pick(p, T, e, p.task_state2[e], p.task_steps2[e], nsteps, b, first, is2d);
-    else {
-        speaks = group_pick(p, T, e, p.task_state[e], p.task_steps[e], nsteps, b, first, is2d);
-        if (!speaks && ran < 0 && p.task_state2) {
-            b = sent::Slots();
-            speaks = group_pick(p, T, e, p.task_state2[e], p.task_steps2[e], nsteps, b, first, is2d);
-        }
-    }
+    bool first = false, is2d = false;
+    const bool speaks = sent::pick_env(T, w, cell, b, first, is2d);
     int32_t *row = p.ids + (size_t)e * (size_t)p.max_len;
     int32_t n = -1;
     if (speaks) {
         DevDraw d;
         d.first = first;
         d.st.init(p.seed, p.gid0 + (uint32_t)e, p.episode[e], 3u);
-        if (is2d) d.st.blk = 4u * (uint32_t)nsteps;          // language.sentence_2d: blocks 4 * num_steps onwards
+        if (is2d) d.st.blk = 4u * (uint32_t)w.num_steps;     // language.sentence_2d: blocks 4 * num_steps onwards
         DevEmit out{row, p.max_len};
         n = sent::expand(T, b, d, stack + threadIdx.x, SENT_BLOCK, out);
     }
@@ -107,25 +92,6 @@ __global__ __launch_bounds__(SENT_BLOCK) void xw_sentence_ids_kernel(SentIdsPara
     }
     for (int32_t k = n; k < p.max_len; ++k) row[k] = p.pad_id;
     p.len[e] = n;
-}
-
-struct HostEmit {
-    std::vector<int32_t> *out;
-    void operator()(int32_t, int32_t w) { out->push_back(w); }
-};
-
-struct HostDraw {
-    lang::Stream *st;
-    uint32_t operator()(uint32_t n) { return st ? st->below(n) : 0u; }
-};
-
-std::string sent_names_check(const char *const *names, int32_t n, std::vector<std::string> &out) {
-    if (n < 0 || (n > 0 && !names)) return "NULL argument";
-    for (int32_t i = 0; i < n; ++i) {
-        if (!names[i]) return "NULL name";
-        out.push_back(names[i]);
-    }
-    return "";
 }
 
 }  // namespace
@@ -235,36 +201,13 @@ int xwb_language_sentence_ids(int32_t task, int32_t stage, int32_t event, const 
                               uint32_t episode, uint32_t num_steps, const char *const *words, int32_t n_words, int32_t unk_id,
                               int32_t fold_case, int32_t *ids, int32_t cap, int32_t *need) {
     if (!need || cap < 0 || (cap > 0 && !ids)) return fail(XWB_ERR_ARG, "NULL argument");
-    std::vector<std::string> goals, inames, icolors;
-    std::string err = sent_names_check(goal_names, n_goal_names, goals);
-    if (!err.empty()) return fail(XWB_ERR_ARG, err);
     lang::Vocab v;
-    err = lang::make_vocab(words, n_words, unk_id, fold_case, v);
-    if (!err.empty()) return fail(XWB_ERR_ARG, err);
-    const bool is2d = task == 5 || task == 7;
-    if (is2d && event != 3) {                                  // one icon: the target's name and colour
-        if (name_a >= (uint32_t)n_goal_names) return fail(XWB_ERR_ARG, "name_a out of range");
-        if (task == 7 && !color) return fail(XWB_ERR_ARG, "NULL colour");
-        inames.push_back(goals[name_a]);
-        icolors.push_back(color ? color : "na");
-    }
-    lang::SentLayout L;
-    err = lang::compile_sentence_tables(v, goals, inames, icolors, L);
-    if (!err.empty()) return fail(XWB_ERR_ARG, err);
-    L.lay.t = L.tab.data();
-    sent::Slots b;
-    bool first = false;
-    const bool speaks = is2d ? sent::pick_2d(L.lay, task, event == 3, 0, b, first)
-                             : sent::pick_3d(L.lay, task, stage, event, name_a, name_b, direction, b, first);
+    std::string err = lang::make_vocab(words, n_words, unk_id, fold_case, v);
     std::vector<int32_t> out;
-    if (speaks) {
-        lang::Stream st(seed, gid, episode, 3);
-        if (is2d) st.blk = 4 * num_steps;
-        HostDraw d{first ? nullptr : &st};
-        HostEmit e{&out};
-        int32_t stack[sent::STACK_MAX];
-        if (sent::expand(L.lay, b, d, stack, 1, e) < 0) return fail(XWB_ERR_ARG, "sentence expansion out of range");
-    }
+    if (err.empty())
+        err = lang::hook_sentence(v, task == 5 || task == 7, task, stage, event, goal_names, n_goal_names, name_a, name_b, direction, color,
+                                  seed, gid, episode, num_steps, out);
+    if (!err.empty()) return fail(XWB_ERR_ARG, err);
     *need = (int32_t)out.size();
     for (int32_t k = 0; k < *need && k < cap; ++k) ids[k] = out[k];
     return XWB_OK;

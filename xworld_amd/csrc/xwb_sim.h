@@ -176,6 +176,11 @@ struct xwb_sim {
     // xwb_set_names: the strings behind the name ids (the teacher's sentences are built from them)
     std::vector<std::string> goal_names, icon_names, icon_colors;
     bool have_names = false;
+    // ... and the grammar tables compiled with them under an interning vocabulary, host only (xwb_language.h): xwb_sentence and
+    // the state packets walk sent_host_lay and look the ids up in sent_words
+    std::vector<int32_t> sent_host_tab;
+    std::vector<std::string> sent_words;
+    xwb::sent::SentTab sent_host_lay{};
     // xwb_set_vocabulary / xwb_sentence_ids (xwb_sentence_ids.hip): the caller's words, and the grammar tables compiled with them
     // and with the names above, uploaded to d_sent_tab (rebuilt when either changes)
     std::vector<std::string> vocab_words;
