@@ -123,6 +123,39 @@ def test_foreign_streams_with_work_in_flight(extra):
     torch.cuda.synchronize()
 
 
+@pytest.mark.parametrize("extra", [pytest.param({"visible_radius": 3, "color": True}, id="ego_span"),
+                                   pytest.param({"visible_radius": 1}, id="ego_per_env"),
+                                   pytest.param({"obs_format": "float32"}, id="float32")])
+def test_epochs_and_events_agree_after_every_verb(extra):
+    """The reset routines beside the egocentric span render, the per-env egocentric render and the full-observation render of
+    the classic path (float32 frames), each in both hand-over forms: two batches, one on epochs and one on events, leave the
+    same frames, rewards, codes and episode counters after every verb.  max_steps = 6: most steps finish envs."""
+    torch = _torch()
+    from xworld_amd.batched import BatchedSimulator
+    opts = {"xwd_conf_path": CONF, "task_mode": "lang_acquisition", "max_dim": 7, "max_steps": 6}
+    opts.update(extra)
+    a, b = (BatchedSimulator("xworld", dict(opts, queue_sync=mode), num_envs=256, seed=3, policy_seed=4) for mode in ("epochs", "events"))
+    assert a.queue_sync_mode() == ("epochs", "config") and b.queue_sync_mode() == ("events", "config")
+
+    def same(what):
+        for name in ("obs", "reward", "game_over_codes", "episode"):
+            assert torch.equal(getattr(a, name), getattr(b, name)), (what, name)
+
+    finished = 0
+    for t in range(40):
+        for sim in (a, b):
+            sim.step_autoreset() if t % 4 == 3 else sim.step()
+        same((t, "step"))
+        finished += int((a.game_over_codes != 0).sum())
+        for sim in (a, b):
+            sim.reset_done()
+        same((t, "reset_done"))
+    assert finished > 256                      # (the lists were not empty: every env finished more than once)
+    assert a.check_errors() == 0 and b.check_errors() == 0
+    a.close()
+    b.close()
+
+
 def test_beside_a_live_rccl_communicator():
     """RCCL creates its own streams / hardware queues; a single-rank group is what one device allows."""
     torch = _torch()

@@ -20,6 +20,26 @@ struct Writer {
     void str(const char *s) { size_t len = strlen(s); u64(len); put(s, len + 1); }
 };
 
+// Redraw one env out of turn (map replay, a pose set by hand), the device idle: a one-entry done list, drawn as a first frame
+// (fresh = 2).  The list and its counter are left empty: the next xwb_reset_done rebuilds them from done[].
+int redraw_env(xwb_sim *s, int32_t env) {
+    XwParams p = xw_params(s);
+    const int32_t cnt = 1;
+    const uint8_t two = 2;
+    HIP_TRY(hipMemcpy(p.done_list, &env, 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p.done_count, &cnt, 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->d_fresh + env, &two, 1, hipMemcpyHostToDevice));
+    if (p.visible_radius) HIP_TRY(launch_xw_warp_goals(p, true, nullptr));
+    HIP_TRY(launch_xw_render(p, RENDER_LIST, nullptr));
+    // (xwb_xw_pack_grids: one env redrawn out of turn -- a context ring elsewhere cannot follow that: context > 1 must
+    // re-synchronise with the screens)
+    s->frame_src = PACK_SRC_LIVE; s->draws_since_pack += 2;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemset(p.done_count, 0, 4));
+    s->list_valid = false;
+    return XWB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -262,7 +282,7 @@ int xwb_xw_load_map_task(xwb_sim *s, int32_t env, const uint16_t *grid_host, int
         if (goals > XW_MAX_GOALS) return fail(XWB_ERR_ARG, "a map holds at most 16 goals");
     }
     HIP_TRY(hipDeviceSynchronize());
-    s->shadow_ok = false; s->regen_pending = false; s->regen_deferred = false; s->snap_ok = false;
+    pregen_invalidate(s);
     const size_t cells = (size_t)D * D;
     int32_t axy = agent_x | (agent_y << 16);
     const bool is2d = task >= XWB_TASK2D_TARGET;
@@ -321,27 +341,14 @@ int xwb_xw_load_map_task(xwb_sim *s, int32_t env, const uint16_t *grid_host, int
         }
     }
     int32_t zero = 0;
-    uint8_t z8 = 0, one = 2;
+    uint8_t z8 = 0;
     HIP_TRY(hipMemcpy(s->d_grid + (size_t)env * cells, grid_host, cells * 2, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->d_agent + env, &axy, 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->d_task_state + env, &ts, 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->d_task_steps + env, &zero, 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->d_num_steps + env, &zero, 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->d_done + env, &z8, 1, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_fresh + env, &one, 1, hipMemcpyHostToDevice));
-    // init_screen of that env: render the one-entry list
-    XwParams p = xw_params(s);
-    int32_t cnt = 1;
-    HIP_TRY(hipMemcpy(p.done_list, &env, 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p.done_count, &cnt, 4, hipMemcpyHostToDevice));
-    if (p.visible_radius) HIP_TRY(launch_xw_warp_goals(p, true, nullptr));
-    HIP_TRY(launch_xw_render(p, RENDER_LIST, nullptr));
-    s->frame_src = 0; s->draws_since_pack += 2;            // (xwb_xw_pack_grids: one env redrawn out of turn -- a context ring elsewhere
-                                                           //  cannot follow that: context > 1 must re-synchronise with the screens)
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(p.done_count, 0, 4));
-    s->list_valid = false;
-    return XWB_OK;
+    return redraw_env(s, env);                              // init_screen of that env
 }
 
 int xwb_xw_load_map(xwb_sim *s, int32_t env, const uint16_t *grid_host, int32_t agent_x, int32_t agent_y,
@@ -407,20 +414,7 @@ int xwb_xw_refresh_obs(xwb_sim *s, int32_t env) {
     if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_STATE, "not an xworld batch");
     if (env < 0 || env >= s->n) return fail(XWB_ERR_ARG, "env out of range");
     HIP_TRY(hipDeviceSynchronize());
-    XwParams p = xw_params(s);
-    const int32_t cnt = 1;
-    const uint8_t two = 2;
-    HIP_TRY(hipMemcpy(p.done_list, &env, 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p.done_count, &cnt, 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_fresh + env, &two, 1, hipMemcpyHostToDevice));
-    if (p.visible_radius) HIP_TRY(launch_xw_warp_goals(p, true, nullptr));
-    HIP_TRY(launch_xw_render(p, RENDER_LIST, nullptr));
-    s->frame_src = 0; s->draws_since_pack += 2;            // (xwb_xw_pack_grids: one env redrawn out of turn -- a context ring elsewhere
-                                                           //  cannot follow that: context > 1 must re-synchronise with the screens)
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemset(p.done_count, 0, 4));
-    s->list_valid = false;
-    return XWB_OK;
+    return redraw_env(s, env);
 }
 
 int xwb_race_set_car(xwb_sim *s, int32_t env, float x, float y, float angle) {

@@ -227,7 +227,11 @@ bool epoch_probe(xwb_sim *s, hipStream_t st, int *reason);
 bool side_beside(xwb_sim *s, hipStream_t st, int *reason);
 // -1: the environment / a tool does not override the hand-over mode, 0: events, 1: epochs
 int queue_sync_env(int *reason);
-// what a step call leaves behind is void (the live state was replaced): nothing of it is pending any more
+// the host wrote live state with the device idle (xwb_xw_load_map_task): the pre-generated episodes and the look-ahead
+// snapshot no longer follow from it, and no regeneration pass is in flight.  The step record stays: the queues still hold what
+// it says (xwb_gather_results_beside after a map replay waits for the same epoch as before it).
+void pregen_invalidate(xwb_sim *s);
+// ... and what a step call leaves behind is void as well (the whole live state was replaced): nothing of it is pending any more
 void step_record_invalidate(xwb_sim *s);
 void timer_begin(xwb_sim *s, KernelTimer &t, hipStream_t st);
 void timer_end(xwb_sim *s, KernelTimer &t, hipStream_t st);

@@ -258,10 +258,14 @@ int order_after(xwb_sim *s, const HandOver &h, bool by_epoch, uint32_t epoch, hi
     return XWB_OK;
 }
 
+void pregen_invalidate(xwb_sim *s) {
+    s->shadow_ok = false; s->regen_pending = false; s->regen_deferred = false; s->snap_ok = false;
+}
+
 void step_record_invalidate(xwb_sim *s) {
     s->rec.path = XWB_PATH_NONE;
     s->rec.step_pub_queued = false;
-    s->shadow_ok = false; s->regen_pending = false; s->regen_deferred = false; s->snap_ok = false;
+    pregen_invalidate(s);
 }
 
 // A regeneration pass of xwb_step_autoreset may still be reading the done list and the episode counters on the side queue:
@@ -300,58 +304,21 @@ int flush_regen(xwb_sim *s) {
     return launch_regen(s, s->rec.epochs);
 }
 
-// xworld: reset the compacted list (or all), then re-render those envs.
-// `beside_render`: the list comes from the step kernel that was just launched on `st` followed by render_all;
-// the (latency-bound, two-wavefront) reset kernel then runs on the side stream as soon as the step kernel is
-// done, i.e. *beside* render_all.  render_all may read grid rows of finished envs while they are being
-// regenerated; those envs' frames are rewritten in full by render(list) below, which waits for both.
-int xw_reset_list(xwb_sim *s, int mode, hipStream_t st, bool beside_render = false) {
-    XWB_TRY(join_regen(s, st));
-    s->frame_src = mode == MODE_RESET_ALL ? PACK_SRC_LIVE : PACK_SRC_LIST;
-    s->draws_since_pack += 1;
-    if (s->shadow_ok) s->shadow_breaks += 1;
-    s->shadow_ok = false;                  // the episodes these envs start now are the ones their shadows held
-    s->snap_ok = false;                    // ... and the live grids are rewritten without the snapshot
-    XwParams p = xw_params(s);
-    // beside work already queued on `st` that may still read this step's codes: the list render, ordered on `st` after that
-    // work, clears them
-    p.auto_reset = beside_render ? AUTO_RESET_BY_LIST : AUTO_RESET_CLEAR;
-    hipStream_t rs = beside_render ? s->side : st;
-    // egocentric span path: the map generator only has to wait for the kernel that reads the grids; the goal images are redrawn
-    // by the list render's first launch, beside the cell tables, once the step's term gather is through (it shares their buffers)
-    const bool split = beside_render && s->rec.path == XWB_PATH_EGO_SPAN;
-    const bool span_epochs = split && s->rec.epochs;
-    // full observation: the side queue's kernel waits for the step kernel's epoch, the list render for the reset kernel's; the
-    // publishers are the step call's kernels, already enqueued
-    const bool by_epoch = beside_render && s->rec.epochs && s->rec.step_pub_queued && !p.visible_radius && mode != MODE_RESET_ALL;
-    if (beside_render) XWB_TRY(order_after(s, split ? SPAN_CELLS_DONE : STEP_DONE, by_epoch || span_epochs, s->epoch_step, s->side));
-    timer_begin(s, s->t_reset, rs);
-    HIP_TRY(launch_xw_reset(p, mode, rs));
-    if (p.visible_radius && !split) HIP_TRY(launch_xw_warp_goals(p, mode != MODE_RESET_ALL, rs));
-    timer_end(s, s->t_reset, rs);
-    if (split) {
-        // the map generator and the front kernels of the new episodes' first frames run on the side queue, beside the big
-        // gather (they write nothing the caller reads).  Only the short gather that stores those frames runs on the CALLER's
-        // stream: it overwrites the terminal frames, which work queued there before this call may still read (xwb.h xwb_reset_done).
-        XWB_TRY(order_after(s, TERM_DONE, span_epochs, s->epoch_step, rs));
-        HIP_TRY(launch_xw_render(p, RENDER_LIST_FRONT_WARP, rs));
-    }
-    if (beside_render) {
-        const bool ep = by_epoch || span_epochs;
-        if (ep) next_epoch(s->epoch_reset);
-        XWB_TRY(publish(s, RESET_DONE, ep, s->epoch_reset, s->side));
-        if (by_epoch) p.wait_epoch = s->epoch_reset;                 // (the list render waits for it itself)
-        else XWB_TRY(order_after(s, RESET_DONE, ep, s->epoch_reset, st));
-    }
-    if (mode == MODE_RESET_ALL) {
-        timer_begin(s, s->t_render, st);
-        HIP_TRY(launch_xw_render(p, RENDER_ALL, st));
-        timer_end(s, s->t_render, st);
-    } else {
-        timer_begin(s, s->t_list, st);
-        HIP_TRY(launch_xw_render(p, split ? RENDER_LIST_GATHER : RENDER_LIST, st));
-        timer_end(s, s->t_list, st);
-    }
+// ---- pieces the reset routines and xwb_step_autoreset share ----
+// the map generator for the envs `mode` selects and, under egocentric observation off the span path, their goal images; timed
+int launch_reset(xwb_sim *s, const XwParams &p, int mode, bool warp, hipStream_t q) {
+    timer_begin(s, s->t_reset, q);
+    HIP_TRY(launch_xw_reset(p, mode, q));
+    if (warp) HIP_TRY(launch_xw_warp_goals(p, mode != MODE_RESET_ALL, q));
+    timer_end(s, s->t_reset, q);
+    return XWB_OK;
+}
+
+// a render under timer `t` (t_render: every env / the alive ones; t_list: the first frames of the listed envs)
+int launch_render(xwb_sim *s, KernelTimer &t, const XwParams &p, RenderMode how, hipStream_t q) {
+    timer_begin(s, t, q);
+    HIP_TRY(launch_xw_render(p, how, q));
+    timer_end(s, t, q);
     return XWB_OK;
 }
 
@@ -390,9 +357,7 @@ bool is_lazy(int path) { return path == XWB_PATH_LAZY || path == XWB_PATH_LAZY_F
 // XWB_PATH_PREGEN: every env from its live grid; the render publishes the step epoch, the regeneration pass follows it
 int step_pregen(xwb_sim *s, XwParams &p, bool epochs, hipStream_t st) {
     if (!epochs) { p.sig_epoch = 0; XWB_TRY(publish(s, STEP_DONE, false, 0, st)); }
-    timer_begin(s, s->t_render, st);
-    HIP_TRY(launch_xw_render(p, RENDER_ALL, st));
-    timer_end(s, s->t_render, st);
+    XWB_TRY(launch_render(s, s->t_render, p, RENDER_ALL, st));
     return launch_regen(s, epochs);
 }
 
@@ -405,22 +370,15 @@ int step_pregen(xwb_sim *s, XwParams &p, bool epochs, hipStream_t st) {
 int step_autoreset_classic(xwb_sim *s, XwParams &p, bool epochs, bool span, hipStream_t st) {
     const bool ep = epochs && (!p.visible_radius || span);
     if (!ep) { p.sig_epoch = 0; XWB_TRY(publish(s, STEP_DONE, false, 0, st)); }
-    timer_begin(s, s->t_render, st);
-    HIP_TRY(launch_xw_render(p, RENDER_ALIVE, st));
-    timer_end(s, s->t_render, st);
+    XWB_TRY(launch_render(s, s->t_render, p, RENDER_ALIVE, st));
     XWB_TRY(order_after(s, STEP_DONE, ep, s->epoch_step, s->side));
     if (ep) next_epoch(s->epoch_reset);
     XwParams pr = xw_params(s);
     pr.sig_epoch = 0; pr.auto_reset = AUTO_RESET_KEEP;
     // (span path: the goal images of the reset envs are redrawn in the list render's first launch, beside their cell tables;
     // nothing else reads them -- the big render's kernels skip the finished envs)
-    timer_begin(s, s->t_reset, s->side);
-    HIP_TRY(launch_xw_reset(pr, MODE_RESET_DONE, s->side));
-    if (pr.visible_radius && !span) HIP_TRY(launch_xw_warp_goals(pr, true, s->side));
-    timer_end(s, s->t_reset, s->side);
-    timer_begin(s, s->t_list, s->side);
-    HIP_TRY(launch_xw_render(pr, span ? RENDER_LIST_WARP : RENDER_LIST, s->side));
-    timer_end(s, s->t_list, s->side);
+    XWB_TRY(launch_reset(s, pr, MODE_RESET_DONE, pr.visible_radius && !span, s->side));
+    XWB_TRY(launch_render(s, s->t_list, pr, span ? RENDER_LIST_WARP : RENDER_LIST, s->side));
     XWB_TRY(publish(s, RESET_DONE, ep, s->epoch_reset, s->side));      // queued behind the list render
     return order_after(s, RESET_DONE, ep, s->epoch_reset, st);
 }
@@ -533,6 +491,146 @@ int do_step(xwb_sim *s, const int32_t *actions_dev, int32_t act_rep, bool autore
     return XWB_OK;
 }
 
+// ---- the reset side ----
+// Which queue timeline a reset verb runs, decided once (run_reset).
+enum ResetPath {
+    RESET_ON_CALLER,         // everything on the caller's stream: the whole batch, a mask, a rebuilt list, or the done list of a lazy
+                             // step whose shadows another verb made stale
+    RESET_BESIDE_FULL,       // the done list of the step just queued: map generator on the internal queue beside render_all
+    RESET_BESIDE_SPAN,       // ... beside the egocentric span render, with its three hand-overs
+    RESET_BESIDE_PER_ENV,    // ... beside the per-env egocentric render
+    RESET_INSTALL,           // after a lazy / fused step: the list render installs the pre-generated episodes
+};
+struct ResetPlan {
+    ResetPath path;
+    bool epochs;             // the routine's hand-overs are epochs
+};
+
+ResetPlan choose_reset(xwb_sim *s, int mode) {
+    ResetPlan k{RESET_ON_CALLER, false};
+    // only the list the last step call left, untouched since, can be reset beside (or installed behind) that call's render
+    if (mode != MODE_RESET_DONE || !s->list_valid) return k;
+    if (is_lazy(s->rec.path)) {
+        // (a lazy step's render reads the live grid: the classic reset may not rewrite it beside that render)
+        if (!s->shadow_ok) return k;
+        k.path = RESET_INSTALL;
+    } else if (!s->cfg.visible_radius) k.path = RESET_BESIDE_FULL;
+    else k.path = s->rec.path == XWB_PATH_EGO_SPAN ? RESET_BESIDE_SPAN : RESET_BESIDE_PER_ENV;
+    // Epochs need a publisher that is already in the caller's queue.  The installing list render is its own (it publishes the
+    // fused step's epoch itself); the span render's front kernels publish sync[SYNC_SPAN_*] in every step call on epochs; under
+    // full observation it is the kernel behind the step kernel, which a fused launch does not have.  The per-env egocentric
+    // render hands over through events.
+    k.epochs = s->rec.epochs && (k.path == RESET_INSTALL || k.path == RESET_BESIDE_SPAN || (!s->cfg.visible_radius && s->rec.step_pub_queued));
+    return k;
+}
+
+// What every reset that regenerates live envs does first.
+int reset_preamble(xwb_sim *s, int frame_src, hipStream_t st) {
+    XWB_TRY(join_regen(s, st));
+    s->frame_src = frame_src;
+    s->draws_since_pack += 1;
+    if (s->shadow_ok) s->shadow_breaks += 1;
+    s->shadow_ok = false;                  // the episodes these envs start now are the ones their shadows held
+    s->snap_ok = false;                    // ... and the live grids are rewritten without the snapshot
+    return XWB_OK;
+}
+
+// the done list again from done[] (MODE_RESET_DONE) or from `mask` (MODE_RESET_MASK), into the current list and counter
+int rebuild_done_list(xwb_sim *s, int mode, const uint8_t *mask, hipStream_t st) {
+    XWB_TRY(join_regen(s, st));
+    XwParams p = xw_params(s);
+    p.mask = mask;
+    HIP_TRY(hipMemsetAsync(p.done_count, 0, sizeof(int32_t), st));
+    HIP_TRY(launch_xw_compact(p, mode, st));
+    return XWB_OK;
+}
+
+// RESET_ON_CALLER: map generator, goal images, frames, one after the other on `st`; the reset kernel clears the codes
+int reset_on_caller(xwb_sim *s, int mode, hipStream_t st) {
+    XWB_TRY(reset_preamble(s, mode == MODE_RESET_ALL ? PACK_SRC_LIVE : PACK_SRC_LIST, st));
+    XwParams p = xw_params(s);
+    p.auto_reset = AUTO_RESET_CLEAR;
+    XWB_TRY(launch_reset(s, p, mode, p.visible_radius != 0, st));
+    if (mode == MODE_RESET_ALL) return launch_render(s, s->t_render, p, RENDER_ALL, st);
+    return launch_render(s, s->t_list, p, RENDER_LIST, st);
+}
+
+// RESET_BESIDE_FULL, RESET_BESIDE_PER_ENV: the list comes from the step kernel that was just launched on `st` followed by the
+// big render; the (latency-bound, two-wavefront) reset kernel runs on the internal queue as soon as the step kernel is done, i.e.
+// *beside* that render.  Under full observation render_all may read grid rows of finished envs while they are being
+// regenerated; those envs' frames are rewritten in full by the list render below, which waits for both.  The per-env
+// egocentric render skips the finished envs (their terminal frames were drawn behind the step kernel: step_plain); there the
+// goal images follow the map generator, and the hand-overs are events (choose_reset).
+int reset_beside_render(xwb_sim *s, bool epochs, hipStream_t st) {
+    XWB_TRY(reset_preamble(s, PACK_SRC_LIST, st));
+    XwParams p = xw_params(s);
+    // work already queued on `st` may still read this step's codes: the list render, ordered on `st` after that work, clears them
+    p.auto_reset = AUTO_RESET_BY_LIST;
+    // (epochs: the publisher is the step call's kernel behind the step kernel, already enqueued)
+    XWB_TRY(order_after(s, STEP_DONE, epochs, s->epoch_step, s->side));
+    XWB_TRY(launch_reset(s, p, MODE_RESET_DONE, p.visible_radius != 0, s->side));
+    if (epochs) next_epoch(s->epoch_reset);
+    XWB_TRY(publish(s, RESET_DONE, epochs, s->epoch_reset, s->side));
+    if (epochs) p.wait_epoch = s->epoch_reset;                       // (the list render waits for it itself)
+    else XWB_TRY(order_after(s, RESET_DONE, false, 0, st));
+    return launch_render(s, s->t_list, p, RENDER_LIST, st);
+}
+
+// RESET_BESIDE_SPAN: the map generator only has to wait for the kernel that reads the grids; the goal images are redrawn by the
+// list render's first launch, beside the cell tables, once the step's term gather is through (it shares their buffers).
+int reset_beside_span(xwb_sim *s, bool epochs, hipStream_t st) {
+    XWB_TRY(reset_preamble(s, PACK_SRC_LIST, st));
+    XwParams p = xw_params(s);
+    p.auto_reset = AUTO_RESET_BY_LIST;                               // (as reset_beside_render: the gather on `st` clears the codes)
+    XWB_TRY(order_after(s, SPAN_CELLS_DONE, epochs, s->epoch_step, s->side));
+    XWB_TRY(launch_reset(s, p, MODE_RESET_DONE, false, s->side));
+    // the map generator and the front kernels of the new episodes' first frames run on the side queue, beside the big
+    // gather (they write nothing the caller reads).  Only the short gather that stores those frames runs on the CALLER's
+    // stream: it overwrites the terminal frames, which work queued there before this call may still read (xwb.h xwb_reset_done).
+    XWB_TRY(order_after(s, TERM_DONE, epochs, s->epoch_step, s->side));
+    HIP_TRY(launch_xw_render(p, RENDER_LIST_FRONT_WARP, s->side));
+    if (epochs) next_epoch(s->epoch_reset);
+    XWB_TRY(publish(s, RESET_DONE, epochs, s->epoch_reset, s->side));
+    XWB_TRY(order_after(s, RESET_DONE, epochs, s->epoch_reset, st));
+    return launch_render(s, s->t_list, p, RENDER_LIST_GATHER, st);
+}
+
+// RESET_INSTALL: the step kept no terminal snapshot and every env's next episode is pre-generated: the list render installs the
+// shadows of the finished envs and draws their first frames (st); the side queue regenerates what was consumed, for nobody in
+// particular -- the next holder of the done list waits for it device-side.  The shadows stay valid: no reset_preamble.
+int reset_install(xwb_sim *s, bool epochs, hipStream_t st) {
+    const bool fused = s->rec.path == XWB_PATH_LAZY_FUSED;
+    s->frame_src = PACK_SRC_LIST; s->draws_since_pack += 1;
+    XwParams p = xw_params(s);
+    p.auto_reset = AUTO_RESET_BY_LIST; p.list_swap = 1;
+    // the installs go to the live state AND to the snapshot of it that the next fused step draws from
+    if (s->snap_ok) { p.snap_grid_out = s->d_snap_grid[s->snap_sel]; p.snap_act_rep = s->snap_act_rep; }
+    // after a fused step this render is the first kernel behind the step in the caller's queue: it publishes that step's epoch
+    p.sig_epoch = fused && epochs ? s->epoch_step : 0;
+    if (p.sig_epoch) s->rec.step_pub_queued = true;
+    // the shadows it installs are the last regeneration pass's: the render waits for its epoch itself, an event is joined here
+    if (s->regen_pending && !s->regen_by_epoch) XWB_TRY(join_regen(s, st));
+    p.wait_slot = SYNC_REGEN;
+    p.wait_epoch = s->regen_pending ? s->epoch_regen : 0;
+    XWB_TRY(launch_render(s, s->t_list, p, RENDER_LIST, st));
+    // Behind a fused step + render launch the regeneration cannot start before this list render does (it publishes the step's
+    // epoch), and nothing needs it before the next step call: it is queued at the top of that call (flush_regen), where it
+    // runs beside the render exactly as it would from here -- but a caller that synchronises the device after this verb
+    // does not wait 70 us for pre-generated episodes nobody has asked for yet.
+    if (fused) { s->regen_deferred = true; return XWB_OK; }
+    return launch_regen(s, epochs);
+}
+
+// the xworld half of xwb_reset / xwb_reset_done / xwb_reset_masked (and through it xwb_reset_env), the list in place
+int run_reset(xwb_sim *s, int mode, hipStream_t st) {
+    const ResetPlan k = choose_reset(s, mode);
+    s->list_valid = false;
+    if (k.path == RESET_ON_CALLER) return reset_on_caller(s, mode, st);
+    if (k.path == RESET_BESIDE_SPAN) return reset_beside_span(s, k.epochs, st);
+    if (k.path == RESET_INSTALL) return reset_install(s, k.epochs, st);
+    return reset_beside_render(s, k.epochs, st);                     // (full observation, or the per-env egocentric render)
+}
+
 }  // namespace host
 }  // namespace xwb
 
@@ -545,8 +643,7 @@ int xwb_reset(xwb_sim *s, void *stream) {
     hipStream_t st = as_stream(stream);
     s->autoreset_done = false;
     if (s->cfg.game != XWB_XWORLD2D) return simple_launch(s, MODE_RESET_ALL, nullptr, nullptr, 1, false, 1, st);
-    s->list_valid = false;
-    return xw_reset_list(s, MODE_RESET_ALL, st);
+    return run_reset(s, MODE_RESET_ALL, st);
 }
 
 int xwb_reset_done(xwb_sim *s, void *stream) {
@@ -562,44 +659,9 @@ int xwb_reset_done(xwb_sim *s, void *stream) {
         return XWB_OK;
     }
     if (s->cfg.game != XWB_XWORLD2D) return simple_launch(s, MODE_RESET_DONE, nullptr, nullptr, 1, false, 1, st);
-    if (!s->list_valid) {                      // no step since the last reset: rebuild the list from done[]
-        XWB_TRY(join_regen(s, st));
-        XwParams p = xw_params(s);
-        HIP_TRY(hipMemsetAsync(p.done_count, 0, sizeof(int32_t), st));
-        HIP_TRY(launch_xw_compact(p, MODE_RESET_DONE, st));
-    }
-    const bool lazy = is_lazy(s->rec.path), fused = s->rec.path == XWB_PATH_LAZY_FUSED;
-    if (s->list_valid && lazy && s->shadow_ok) {
-        // the step kept no terminal snapshot and every env's next episode is pre-generated: the list render installs the
-        // shadows of the finished envs and draws their first frames (st); the side queue regenerates what was consumed, for
-        // nobody in particular -- the next holder of the done list waits for it device-side
-        s->list_valid = false;
-        s->frame_src = PACK_SRC_LIST; s->draws_since_pack += 1;
-        XwParams p = xw_params(s);
-        p.auto_reset = AUTO_RESET_BY_LIST; p.list_swap = 1;
-        const bool by_epoch = s->rec.epochs;
-        // (the installs go to the live state AND to the snapshot of it that the next fused step draws from; after a fused step
-        // this render is the first kernel behind the step in the caller's queue: it publishes that step's epoch)
-        if (s->snap_ok) { p.snap_grid_out = s->d_snap_grid[s->snap_sel]; p.snap_act_rep = s->snap_act_rep; }
-        p.sig_epoch = fused && by_epoch ? s->epoch_step : 0;
-        if (p.sig_epoch) s->rec.step_pub_queued = true;
-        if (s->regen_pending && !s->regen_by_epoch) XWB_TRY(join_regen(s, st));
-        p.wait_slot = SYNC_REGEN;
-        p.wait_epoch = s->regen_pending ? s->epoch_regen : 0;
-        timer_begin(s, s->t_list, st);
-        HIP_TRY(launch_xw_render(p, RENDER_LIST, st));
-        timer_end(s, s->t_list, st);
-        // Behind a fused step + render launch the regeneration cannot start before this list render does (it publishes the step's
-        // epoch), and nothing needs it before the next step call: it is queued at the top of that call (flush_regen), where it
-        // runs beside the render exactly as it would from here -- but a caller that synchronises the device after this verb
-        // does not wait 70 us for pre-generated episodes nobody has asked for yet.
-        if (fused) { s->regen_deferred = true; return XWB_OK; }
-        return launch_regen(s, by_epoch);
-    }
-    // (a lazy step's render reads the live grid: the classic reset may not rewrite it beside that render)
-    const bool beside = s->list_valid && !lazy;
-    s->list_valid = false;
-    return xw_reset_list(s, MODE_RESET_DONE, st, beside);
+    // no step since the last reset: the list is rebuilt from done[]
+    if (!s->list_valid) XWB_TRY(rebuild_done_list(s, MODE_RESET_DONE, nullptr, st));
+    return run_reset(s, MODE_RESET_DONE, st);
 }
 
 int xwb_reset_masked(xwb_sim *s, const uint8_t *mask_dev, void *stream) {
@@ -608,13 +670,8 @@ int xwb_reset_masked(xwb_sim *s, const uint8_t *mask_dev, void *stream) {
     XWB_LIVE(s);
     hipStream_t st = as_stream(stream);
     if (s->cfg.game != XWB_XWORLD2D) return simple_launch(s, MODE_RESET_MASK, mask_dev, nullptr, 1, false, 1, st);
-    XWB_TRY(join_regen(s, st));
-    XwParams p = xw_params(s);
-    p.mask = mask_dev;
-    HIP_TRY(hipMemsetAsync(p.done_count, 0, sizeof(int32_t), st));
-    HIP_TRY(launch_xw_compact(p, MODE_RESET_MASK, st));
-    s->list_valid = false;
-    return xw_reset_list(s, MODE_RESET_MASK, st);
+    XWB_TRY(rebuild_done_list(s, MODE_RESET_MASK, mask_dev, st));
+    return run_reset(s, MODE_RESET_MASK, st);
 }
 
 int xwb_reset_env(xwb_sim *s, int32_t env, void *stream) {
