@@ -105,7 +105,7 @@ typedef struct xwb_config {
 
     /* xworld (xworld_simulator.cpp:22-37, teacher.cpp:22-25, simulator.cpp:23-25) */
     int32_t  map_kind;           /* XWB_MAP_* : the "map" key of the conf JSON (xworld.cpp:73-76) */
-    int32_t  max_dim;            /* max_height == max_width of the map class */
+    int32_t  max_dim;            /* max_height == max_width of the map class: up to 16 (15 with the 2-D-native task group) */
     int32_t  dim;                /* actual dim (== max_dim when FLAGS_curriculum == 0) */
     int32_t  num_goals, num_blocks;
     int32_t  max_steps_factor;   /* FLAGS_max_steps_factor (10) */
@@ -394,7 +394,8 @@ int xwb_xw_load_map_task(xwb_sim *sim, int32_t env, const uint16_t *grid_host, i
                          int32_t dim, int32_t task, int32_t target);
 /* egocentric replays: the agent's heading, and the pose (xworld_env.py:207-223: yaw, scale, offset) of the goal at a
  * cell; the warp matrix is derived on the host exactly as XItem::get_item_image does.  Synchronous; call
- * xwb_xw_refresh_obs afterwards to re-render the env. */
+ * xwb_xw_refresh_obs afterwards to re-render the env.  A goal may stand in any cell, the last one of a 16 x 16 map included
+ * (cell 255, the byte the goal-slot table uses for "no goal"). */
 int xwb_xw_set_agent_dir(xwb_sim *sim, int32_t env, int32_t dir);
 int xwb_xw_set_goal_pose(xwb_sim *sim, int32_t env, int32_t cell_x, int32_t cell_y, double yaw, double scale, double offset);
 int xwb_xw_refresh_obs(xwb_sim *sim, int32_t env);

@@ -85,6 +85,66 @@ def test_checker_against_the_oracles_egocentric_pixels(oracle, r, shadow):
         assert met["shadow"] == 0
 
 
+def _masking(is_block, ax, ay, fd, r):
+    """XMap::image_masking (xmap.cpp:273-362) a second time, from the map alone: the window's origin on the map padded by r cells
+    and shadow[window row][window column].  The agent stands in the window's last line along its heading, in the middle across
+    it.  A ray runs from the agent to either side: what lies beyond a block on it starts its scan line in the dark; every scan
+    line then runs away from the agent along the heading, and what lies beyond a block on it is dark."""
+    ahead = {0: (1, 0), 1: (0, 1), 2: (-1, 0), 3: (0, -1)}[fd]
+    across = (abs(ahead[1]), abs(ahead[0]))
+    h = r // 2
+    cx, cy = ax + r + ahead[0] * h, ay + r + ahead[1] * h                   # the window's centre cell, padded coordinates
+    x_st, y_st = cx - h, cy - h
+    lit = [True] * r                                                        # per scan line: it starts in the light
+    for side in (-1, 1):
+        blocked = False
+        for k in range(1, h + 1):
+            if blocked:
+                lit[h + side * k] = False
+            blocked = blocked or is_block(ax + side * k * across[0], ay + side * k * across[1])
+    shadow = np.zeros((r, r), np.uint8)
+    for t in range(r):
+        blocked = not lit[t]
+        for j in range(r):
+            gx = ax + (t - h) * across[0] + j * ahead[0]
+            gy = ay + (t - h) * across[1] + j * ahead[1]
+            shadow[gy + r - y_st, gx + r - x_st] = blocked
+            blocked = blocked or is_block(gx, gy)
+    return x_st, y_st, shadow
+
+
+@pytest.mark.parametrize("r", [13, 15])
+def test_checker_and_masking_at_sixteen_cells(oracle, r):
+    """16 x 16 maps at r = 13 and 15, where the oracle's egocentric render is the r = 3 code run further (unpinned by the
+    reference): 36 views square by square against the checker, and the oracle's window and wall shadows against _masking above,
+    which shares nothing with it but the map.  tests/test_gpu_ego_sizes.py rests on both at these sizes."""
+    pal = oracle.Palette(oracle.NAV_SUBTREES)
+    w = oracle.XWorld(pal, map_kind=0, max_dim=16, dim=16, num_goals=4, num_blocks=60, color=1, visible_radius=r,
+                      tasks=["XWorld3DNavTarget"], seed=77)
+    met = {"shadow": 0, "outside": 0, S.EMPTY: 0, S.GOAL: 0, S.BLOCK: 0, S.AGENT: 0}
+    headings = set()
+    for e in range(12):
+        w.reset_game(e, 0)
+        for s in range(STEPS + 1):
+            exp, inside = S.expected(w, pal, detail=True)
+            fd = S.facing(w.agent_yaw())
+            headings.add(fd)
+            planes = S.map_planes(w, pal)
+            ax, ay = w.agent_xy()
+            x_st, y_st, shadow = _masking(lambda x, y: 0 <= x < 16 and 0 <= y < 16 and planes[S.KIND, y, x] == S.BLOCK, ax, ay, fd, r)
+            ox, oy, oshadow = w.agent_masking()
+            assert (x_st, y_st) == (ox, oy) and np.array_equal(shadow, oshadow), (r, e, s, fd)
+            _check_squares(w.agent_view(), exp, pal, fd, (r, e, s))
+            assert exp[S.KIND, r - 1, r // 2] == S.AGENT and int((exp[S.KIND] == S.AGENT).sum()) == 1
+            dark = exp[S.KIND] == S.DARK
+            met["shadow"] += int((dark & inside).sum())
+            met["outside"] += int((dark & ~inside).sum())
+            for k in (S.EMPTY, S.GOAL, S.BLOCK, S.AGENT):
+                met[k] += int((exp[S.KIND] == k).sum())
+            w.take_actions(oracle.policy_action(5, e, s, w.num_actions()))
+    assert headings == {0, 1, 2, 3} and all(v > 0 for v in met.values()), (headings, met)
+
+
 @pytest.mark.parametrize("key", ["nav7", "nav8_dim5", "walls7"])
 def test_checker_against_the_oracles_full_observation_pixels(oracle, key):
     from test_view_expected import FULL

@@ -130,8 +130,12 @@ __device__ __forceinline__ void ego_cells_body(const XwParams &p, const uint8_t 
     // env's sixteen slots per visible goal (that search was a third of the kernel's instructions)
     for (int i = tid; i < n_here * XW_MAX_GOALS; i += 64 * NW) {
         const int le = i / XW_MAX_GOALS, slot = i - le * XW_MAX_GOALS;
-        const int cell = reinterpret_cast<const uint8_t *>(&s_gc[le])[slot];
-        if (cell < cells) s_type[le * cells + cell] |= (uint8_t)(slot << 2);
+        const uint8_t *gc = reinterpret_cast<const uint8_t *>(&s_gc[le]);
+        const int cell = gc[slot];
+        // (0xff: an empty slot -- but for the first one on a 16 x 16 map whose cell 255 holds a goal, the one lane that then
+        // writes that byte; the type sits in bits 0-1, which no lane changes)
+        if (cell < cells && (cell != 0xff || !xw_goal_slot_empty(gc, slot, (s_type[le * cells + 0xff] & 3) == 0)))
+            s_type[le * cells + cell] |= (uint8_t)(slot << 2);
     }
     __syncthreads();
     EGO_C(1);
@@ -928,7 +932,7 @@ __device__ __forceinline__ void warp_goals_body(const XwParams &p, const uint32_
         // new poses: whatever the render cached of this env's goal cells is stale
         if (slot == 0 && part == 0 && p.ego_cache_valid)
             for (int q = threadIdx.x; q < (int)p.ego_cache_words; q += 256) p.ego_cache_valid[(size_t)e * p.ego_cache_words + q] = 0;
-        if (cell == 0xff) continue;
+        if (xw_goal_slot_empty(p.goal_cells + (size_t)e * XW_MAX_GOALS, slot, D, p.grid + (size_t)e * D * D, p.icon_type)) continue;
         const int icon = (int)(p.grid[(size_t)e * D * D + cell] & CELL_ICON_MASK) - 1;
         if (icon < 0) continue;
         const double *M = p.goal_warp + ((size_t)e * XW_MAX_GOALS + slot) * 6;

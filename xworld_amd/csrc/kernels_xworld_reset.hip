@@ -881,7 +881,7 @@ __device__ void xw_idle3d_env(const XwParams &p, const LaneLds &L, int e) {
     int ng = 0;
     for (int i = 0; i < XW_MAX_GOALS; ++i) {
         const int mc = gc[i];
-        if (mc == 0xff) break;
+        if (xw_goal_slot_empty(gc, i, MD, g, p.icon_type)) break;
         const int icon = (int)(g[mc] & CELL_ICON_MASK) - 1;
         if (icon < 0) break;                               // (cannot happen: the table lists cells that hold goals)
         L.gcell[L.at(i)] = (uint8_t)((mc / MD - off) * D + (mc % MD - off));

@@ -35,6 +35,15 @@ __device__ __forceinline__ uint32_t xw_frame_code(const XwParams &p, bool term, 
     return (term ? p.term_grid[gi] : p.grid[gi]) & CELL_ICON_MASK;
 }
 
+// xw_goal_slot_empty (xwb_common.h) for a reader that holds the env's grid: grid_env = its max_dim * max_dim cell codes (the
+// target bit may be set).
+__device__ __forceinline__ bool xw_goal_slot_empty(const uint8_t *gc, int slot, int max_dim, const uint16_t *grid_env, const uint8_t *icon_type) {
+    if (gc[slot] != 0xff) return false;
+    if (max_dim < 16) return true;
+    const int icon = (int)(grid_env[0xff] & CELL_ICON_MASK) - 1;
+    return xw_goal_slot_empty(gc, slot, icon >= 0 && icon_type[icon] == 0);
+}
+
 // The idle stage of a 2-D-native task (XWorldNavTarget.py:22-33, XWorldNavColorTarget.py:8-20; Near / Between never
 // find a target in this snapshot): Task::reset, then a uniformly chosen reachable [coloured] goal.
 // `draw(n)` supplies the decisions (reset stream at reset time, stream 2 / block = num_steps at step time).

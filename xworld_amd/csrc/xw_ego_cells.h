@@ -96,8 +96,9 @@ __device__ __forceinline__ EgoCell ego_window_cell(const XwParams &p, const uint
         else {
             c = ego_icon_cell(icon_type, agent_rot, atlas4, cd - 1, dir);
             if (type[gy * D + gx] == 0) {               // a goal: this env's warped copy
-                int s = 0;
-                for (int i = 0; i < XW_MAX_GOALS; ++i) if (gc[i] == gy * D + gx) s = i;
+                // the FIRST slot that holds the cell: cell 255 of a 16 x 16 map reads like the empty slots' 0xff, which all
+                // come after the real ones (xwb_common.h, xw_goal_slot_of)
+                const int found = xw_goal_slot_of(gc, gy * D + gx), s = found < 0 ? 0 : found;
                 c.img = gimg + s * 4096;
                 c.tab = -1;
                 *slot = s;

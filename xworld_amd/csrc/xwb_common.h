@@ -192,6 +192,22 @@ constexpr int XW_USAGE_BYTES = 32;  // one task class's success window
 constexpr int XW_TILE = 12;           // block_size, xworld_simulator.cpp:57
 constexpr int XW_TILE_DW = 3;         // dwords per tile row (12 bytes)
 
+// goal_cells (XwParams): one byte per goal slot, the goal's cell, 0xff = "no goal in this slot" -- which is also cell 255 of
+// a 16 x 16 map.  A goal keeps its slot when an idle stage moves it (Near / Between / Direction put two goals on a tile that
+// may end in the last cell), so the goal of cell 255 can sit in ANY of the env's real slots, before other goals; what holds is
+// that the real slots 0 .. ng - 1 all precede the empty ones and that a cell holds one goal at most.  So:
+//   - the slot of a cell that holds a goal is the FIRST entry equal to it (every later 0xff is an empty slot);
+//   - a 0xff entry is a goal iff the grid's cell 255 holds a goal icon AND no earlier entry is 0xff.
+// The one statement of both, for the device's readers and xwb_xw_set_goal_pose.
+__host__ __device__ __forceinline__ int xw_goal_slot_of(const uint8_t *gc, int cell) {
+    for (int i = 0; i < XW_MAX_GOALS; ++i) if (gc[i] == cell) return i;
+    return -1;
+}
+// goal_in_255: the map has 16 x 16 cells and the grid's cell 255 holds a goal icon
+__host__ __device__ __forceinline__ bool xw_goal_slot_empty(const uint8_t *gc, int slot, bool goal_in_255) {
+    return gc[slot] == 0xff && !(goal_in_255 && xw_goal_slot_of(gc, 0xff) == slot);
+}
+
 struct XwParams {
     int n, context, max_steps, act_rep, auto_reset;
     int map_kind, max_dim, dim, num_goals, num_blocks, max_steps_factor, task_mode, channels;

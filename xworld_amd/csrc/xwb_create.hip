@@ -175,9 +175,11 @@ int xw_setup(xwb_sim *s) {
     if (!(c.task_group_weight >= 0) || !(c.task_group_weight2 >= 0)) return fail(XWB_ERR_ARG, "xworld: task group weights must be >= 0");
     const int n = s->n, cells = c.max_dim * c.max_dim, ch = c.color ? 3 : 1;
     const bool group2d_cfg = (c.n_tasks > 0 && c.tasks[0] >= XWB_TASK2D_TARGET) || (c.n_tasks2 > 0 && c.tasks2[0] >= XWB_TASK2D_TARGET);
-    // goal_cells holds one byte per goal slot with 0xff = "no goal": cell 255 only exists on a 16x16 map
-    if (c.max_dim > 15 && (c.visible_radius > 0 || group2d_cfg))
-        return fail(XWB_ERR_ARG, "xworld: max_dim 16 is not available with visible_radius > 0 or the 2-D-native task group (<= 15)");
+    // goal_cells holds one byte per goal slot with 0xff = "no goal": cell 255 only exists on a 16x16 map.  The step kernel, the
+    // expert and the egocentric readers tell the two apart (xwb_common.h, xw_goal_slot_empty); the 2-D-native group's candidate
+    // tables do not
+    if (c.max_dim > 15 && group2d_cfg)
+        return fail(XWB_ERR_ARG, "xworld: max_dim 16 is not available with the 2-D-native task group (<= 15)");
     // name tables (xworld_env.py:247-255): per type, names -> icon variants (icon order = path order)
     int n_names[3] = {0, 0, 0};
     for (int i = 0; i < c.n_icons; ++i) {

@@ -387,8 +387,14 @@ int xwb_xw_set_goal_pose(xwb_sim *s, int32_t env, int32_t cell_x, int32_t cell_y
     HIP_TRY(hipDeviceSynchronize());
     uint8_t gc[XW_MAX_GOALS];
     HIP_TRY(hipMemcpy(gc, s->d_goal_cells + (size_t)env * XW_MAX_GOALS, XW_MAX_GOALS, hipMemcpyDeviceToHost));
-    int slot = -1;
-    for (int i = 0; i < XW_MAX_GOALS; ++i) if (gc[i] == cell_y * D + cell_x) slot = i;
+    const int cell = cell_y * D + cell_x;
+    int slot = xw_goal_slot_of(gc, cell);
+    if (slot >= 0 && cell == 0xff) {                    // cell 255 of a 16 x 16 map reads like an empty slot: ask the grid
+        uint16_t code = 0;
+        HIP_TRY(hipMemcpy(&code, s->d_grid + (size_t)env * D * D + cell, 2, hipMemcpyDeviceToHost));
+        const int icon = (int)(code & XWB_CELL_ICON_MASK) - 1;
+        if (xw_goal_slot_empty(gc, slot, icon >= 0 && icon < s->cfg.n_icons && s->icon_type_h[icon] == XWB_ICON_GOAL)) slot = -1;
+    }
     if (slot < 0) return fail(XWB_ERR_ARG, "no goal at that cell");
     // XItem::get_item_image (xitem.cpp:46-60) + the inversion cv::warpAffine performs
     const double angle = (90 - yaw * 180 / 3.14159265358979323846) * 3.1415926535897932384626433832795 / 180;
