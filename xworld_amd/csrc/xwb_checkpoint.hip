@@ -23,13 +23,14 @@ std::vector<StateArray> state_arrays(xwb_sim *s, bool include_obs, int list_sel,
     add(s->d_minstd, n * 4);
     if (s->cfg.game == XWB_XWORLD2D) {
         const size_t cells = (size_t)s->cfg.max_dim * s->cfg.max_dim;
-        add(s->d_grid, n * cells * 2); add(s->d_agent, n * 4); add(s->d_task_steps, n * 4); add(s->d_task_state, n * 4);
-        add(s->d_task_steps2, n * 4); add(s->d_task_state2, n * 4); add(s->d_grp_order, n);
+        const XwParams &x = s->xw;
+        add(x.grid, n * cells * 2); add(x.agent_xy, n * 4); add(x.task_steps, n * 4); add(x.task_state, n * 4);
+        add(x.task_steps2, n * 4); add(x.task_state2, n * 4); add(x.grp_order, n);
         // (the done list and its counter rotate through two / three buffers: the current ones are saved, a load rewinds the rotation)
-        add(s->d_done_list + (size_t)list_sel * n, n * 4); add(s->d_done_count + count_sel, 4); add(s->d_fresh, n); add(s->d_perf, 40 * 8);
-        add(s->d_goal_cells, n * XW_MAX_GOALS); add(s->d_cand2d, n * 4); add(s->d_agent_dir, n); add(s->d_sent_names, n * 4);
-        add(s->d_goal_warp, n * XW_MAX_GOALS * 6 * sizeof(double));     // goal images are re-warped from these on load
-        add(s->d_cur_level, n); add(s->d_cur_counter, n * 4); add(s->d_cur_usage, n * 9 * XW_USAGE_BYTES);
+        add(x.done_list + (size_t)list_sel * n, n * 4); add(x.done_count + count_sel, 4); add(x.fresh, n); add(x.perf, 40 * 8);
+        add(x.goal_cells, n * XW_MAX_GOALS); add(x.cand2d, n * 4); add(x.agent_dir, n); add(x.sent_names, n * 4);
+        add(x.goal_warp, n * XW_MAX_GOALS * 6 * sizeof(double));        // goal images are re-warped from these on load
+        add(x.cur_level, n); add(x.cur_counter, n * 4); add(x.cur_usage, n * 9 * XW_USAGE_BYTES);
     }
     if (include_obs) add(s->d_obs, n * s->obs_bytes_per_env);
     return a;
@@ -124,7 +125,7 @@ int xwb_load_state(xwb_sim *s, const uint8_t *in_host, size_t bytes) {
     HIP_TRY(hipDeviceSynchronize());
     step_record_invalidate(s);
     s->count_sel = 0; s->list_sel = 0;
-    if (s->d_done_count) HIP_TRY(hipMemset(s->d_done_count, 0, 3 * sizeof(int32_t)));
+    if (s->xw.done_count) HIP_TRY(hipMemset(s->xw.done_count, 0, 3 * sizeof(int32_t)));
     at = sizeof h;
     for (auto &a : arrays) {
         HIP_TRY(hipMemcpy(a.ptr, in_host + at + 8, a.bytes, hipMemcpyHostToDevice));
@@ -136,7 +137,7 @@ int xwb_load_state(xwb_sim *s, const uint8_t *in_host, size_t bytes) {
         XwParams p = xw_params(s);
         if (p.visible_radius) HIP_TRY(launch_xw_warp_goals(p, false, nullptr));
         if (!h.include_obs) {                           // frames from the state; older context frames start black
-            HIP_TRY(hipMemset(s->d_fresh, 2, (size_t)s->n));
+            HIP_TRY(hipMemset(s->xw.fresh, 2, (size_t)s->n));
             HIP_TRY(launch_xw_render(p, RENDER_ALL, nullptr));
         }
     }

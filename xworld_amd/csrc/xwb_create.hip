@@ -130,20 +130,67 @@ void build_tile_table(const uint8_t *icons64, int n_icons, int channels, uint8_t
 
 namespace {
 
-bool curriculum_cfg(const xwb_config &c) { return c.curriculum != 0 && c.map_kind == XWB_MAP_NAV; }
+bool curriculum_cfg(const xwb_config &c) { return c.curriculum != 0 && c.map_kind == XWB_MAP_NAV; }   // XWorldWalls never reads the flag
+// simulator_interface.cpp:46-48: lang_acquisition runs the groups non-exclusively whatever the flag says
+bool exclusive_cfg(const xwb_config &c) { return c.task_groups_exclusive && c.task_mode != XWB_TASKMODE_LANG_ACQ; }
+bool group2d_cfg(const int32_t *tasks, int n) { return n > 0 && tasks[0] >= XWB_TASK2D_TARGET; }
 
-int xw_setup(xwb_sim *s) {
-    const xwb_config &c = s->cfg;
+// name tables (xworld_env.py:247-255): per type, names -> icon variants (icon order = path order)
+struct NameTables {
+    int n_names[3] = {0, 0, 0}, off[3] = {0, 0, 0};      // off: start of each type's offsets inside `first`
+    std::vector<int16_t> first, variants;
+};
+
+int name_tables(const xwb_config &c, NameTables &t) {
+    for (int i = 0; i < c.n_icons; ++i) {
+        const int ty = c.icon_type[i];
+        if (ty < 0 || ty > 2 || c.icon_name[i] < 0) return fail(XWB_ERR_ARG, "xworld: bad icon_type / icon_name");
+        if (c.icon_name[i] + 1 > t.n_names[ty]) t.n_names[ty] = c.icon_name[i] + 1;
+    }
+    if (t.n_names[1] < 1 || t.n_names[2] < 1 || t.n_names[0] < 1)
+        return fail(XWB_ERR_ARG, "xworld: palette needs at least one goal, one block and one agent icon");
+    if (c.map_kind == XWB_MAP_NAV && c.num_goals > t.n_names[0])
+        return fail(XWB_ERR_ARG, "xworld: XWorldNav needs num_goals distinct goal names");
+    for (int ty = 0; ty < 3; ++ty) {
+        t.off[ty] = (int)t.first.size();
+        for (int nm = 0; nm < t.n_names[ty]; ++nm) {
+            t.first.push_back((int16_t)t.variants.size());
+            int cnt = 0;
+            for (int i = 0; i < c.n_icons; ++i)
+                if (c.icon_type[i] == ty && c.icon_name[i] == nm) { t.variants.push_back((int16_t)i); cnt++; }
+            if (cnt == 0) return fail(XWB_ERR_ARG, "xworld: name ids of a type must be dense");
+        }
+        t.first.push_back((int16_t)t.variants.size());
+    }
+    return XWB_OK;
+}
+
+// a task group's list (known ids, all of one family) and its schedule: two checks, because xw_check_config's order -- which
+// decides what a configuration with two mistakes reports -- has other checks between the first group's two
+int check_task_ids(const int32_t *tasks, int n) {
+    for (int i = 0; i < n; ++i)
+        if (tasks[i] < XWB_TASK_TARGET || tasks[i] > XWB_TASK2D_BETWEEN) return fail(XWB_ERR_ARG, "xworld: unknown task id");
+    for (int i = 1; i < n; ++i)
+        if ((tasks[i] >= XWB_TASK2D_TARGET) != (tasks[0] >= XWB_TASK2D_TARGET))
+            return fail(XWB_ERR_ARG, "xworld: a task group holds XWorld3DNav* tasks or 2-D-native XWorldNav* tasks, not both");
+    return XWB_OK;
+}
+int check_task_schedule(int schedule, const double *weights, int n, const char *unknown) {
+    if (schedule != XWB_SCHEDULE_RANDOM && schedule != XWB_SCHEDULE_WEIGHTED) return fail(XWB_ERR_ARG, unknown);
+    if (schedule == XWB_SCHEDULE_WEIGHTED)
+        for (int i = 0; i < n; ++i)
+            if (!(weights[i] > 0)) return fail(XWB_ERR_ARG, "A task must have a positive weight");   // teaching_task.cpp:148
+    return XWB_OK;
+}
+
+// every check of an XWorld2D configuration, no device call; leaves the name tables it has to build on the way
+int xw_check_config(const xwb_config &c, NameTables &names) {
     if (c.max_dim < 1 || c.max_dim > XW_MAX_DIM || c.dim < 1 || c.dim > c.max_dim)
         return fail(XWB_ERR_ARG, "xworld: need 1 <= dim <= max_dim <= 16");
     if (c.num_goals < 1 || c.num_goals > XW_MAX_GOALS) return fail(XWB_ERR_ARG, "xworld: need 1 <= num_goals <= 16");
-    if (c.task_schedule != XWB_SCHEDULE_RANDOM && c.task_schedule != XWB_SCHEDULE_WEIGHTED) return fail(XWB_ERR_ARG, "xworld: unknown task_schedule");
-    if (c.task_schedule == XWB_SCHEDULE_WEIGHTED) {
-        if (c.n_tasks < 1) return fail(XWB_ERR_ARG, "xworld: the weighted schedule needs the task list");
-        for (int i = 0; i < c.n_tasks; ++i)
-            if (!(c.task_weights[i] > 0)) return fail(XWB_ERR_ARG, "A task must have a positive weight");   // teaching_task.cpp:148
-    }
-    if (c.curriculum != 0 && c.map_kind == XWB_MAP_NAV) {
+    if (c.task_schedule == XWB_SCHEDULE_WEIGHTED && c.n_tasks < 1) return fail(XWB_ERR_ARG, "xworld: the weighted schedule needs the task list");
+    XWB_TRY(check_task_schedule(c.task_schedule, c.task_weights, c.n_tasks, "xworld: unknown task_schedule"));
+    if (curriculum_cfg(c)) {
         // XWorldNav.py:27-30: six levels, dims 3 .. max_h -- the class asserts n_levels == 6, i.e. its 8x8 world
         if (c.max_dim != 8) return fail(XWB_ERR_ARG, "xworld: curriculum != 0 needs XWorldNav's 8x8 world (max_dim 8)");
         if (c.start_level < 0 || c.start_level > 5) return fail(XWB_ERR_ARG, "xworld: start_level must be in 0..5");
@@ -152,58 +199,22 @@ int xw_setup(xwb_sim *s) {
         return fail(XWB_ERR_ARG, "xworld: icons64 / icon_type / icon_name are required (the reference loads item_path images)");
     if (c.n_icons > 4000) return fail(XWB_ERR_ARG, "xworld: too many icons");
     if (c.n_tasks < 0 || c.n_tasks > 8) return fail(XWB_ERR_ARG, "xworld: need 0 <= n_tasks <= 8");
-    for (int i = 0; i < c.n_tasks; ++i)
-        if (c.tasks[i] < XWB_TASK_TARGET || c.tasks[i] > XWB_TASK2D_BETWEEN) return fail(XWB_ERR_ARG, "xworld: unknown task id");
-    for (int i = 1; i < c.n_tasks; ++i)
-        if ((c.tasks[i] >= XWB_TASK2D_TARGET) != (c.tasks[0] >= XWB_TASK2D_TARGET))
-            return fail(XWB_ERR_ARG, "xworld: a task group holds XWorld3DNav* tasks or 2-D-native XWorldNav* tasks, not both");
+    XWB_TRY(check_task_ids(c.tasks, c.n_tasks));
     if (c.n_tasks2 < 0 || c.n_tasks2 > 8) return fail(XWB_ERR_ARG, "xworld: need 0 <= n_tasks2 <= 8");
     if (c.n_tasks2 > 0) {
         if (c.n_tasks < 1) return fail(XWB_ERR_ARG, "xworld: a second task group needs a first one");
-        for (int i = 0; i < c.n_tasks2; ++i) {
-            if (c.tasks2[i] < XWB_TASK_TARGET || c.tasks2[i] > XWB_TASK2D_BETWEEN) return fail(XWB_ERR_ARG, "xworld: unknown task id");
-            if ((c.tasks2[i] >= XWB_TASK2D_TARGET) != (c.tasks2[0] >= XWB_TASK2D_TARGET))
-                return fail(XWB_ERR_ARG, "xworld: a task group holds XWorld3DNav* tasks or 2-D-native XWorldNav* tasks, not both");
-        }
-        if ((c.tasks2[0] >= XWB_TASK2D_TARGET) == (c.tasks[0] >= XWB_TASK2D_TARGET))
+        XWB_TRY(check_task_ids(c.tasks2, c.n_tasks2));
+        if (group2d_cfg(c.tasks2, c.n_tasks2) == group2d_cfg(c.tasks, c.n_tasks))
             return fail(XWB_ERR_ARG, "xworld: two task groups: one must hold XWorld3DNav* tasks, the other the 2-D-native ones");
-        if (c.task_schedule2 != XWB_SCHEDULE_RANDOM && c.task_schedule2 != XWB_SCHEDULE_WEIGHTED) return fail(XWB_ERR_ARG, "xworld: unknown task_schedule2");
-        if (c.task_schedule2 == XWB_SCHEDULE_WEIGHTED)
-            for (int i = 0; i < c.n_tasks2; ++i)
-                if (!(c.task_weights2[i] > 0)) return fail(XWB_ERR_ARG, "A task must have a positive weight");
+        XWB_TRY(check_task_schedule(c.task_schedule2, c.task_weights2, c.n_tasks2, "xworld: unknown task_schedule2"));
     }
     if (!(c.task_group_weight >= 0) || !(c.task_group_weight2 >= 0)) return fail(XWB_ERR_ARG, "xworld: task group weights must be >= 0");
-    const int n = s->n, cells = c.max_dim * c.max_dim, ch = c.color ? 3 : 1;
-    const bool group2d_cfg = (c.n_tasks > 0 && c.tasks[0] >= XWB_TASK2D_TARGET) || (c.n_tasks2 > 0 && c.tasks2[0] >= XWB_TASK2D_TARGET);
     // goal_cells holds one byte per goal slot with 0xff = "no goal": cell 255 only exists on a 16x16 map.  The step kernel, the
     // expert and the egocentric readers tell the two apart (xwb_common.h, xw_goal_slot_empty); the 2-D-native group's candidate
     // tables do not
-    if (c.max_dim > 15 && group2d_cfg)
+    if (c.max_dim > 15 && (group2d_cfg(c.tasks, c.n_tasks) || group2d_cfg(c.tasks2, c.n_tasks2)))
         return fail(XWB_ERR_ARG, "xworld: max_dim 16 is not available with the 2-D-native task group (<= 15)");
-    // name tables (xworld_env.py:247-255): per type, names -> icon variants (icon order = path order)
-    int n_names[3] = {0, 0, 0};
-    for (int i = 0; i < c.n_icons; ++i) {
-        int t = c.icon_type[i];
-        if (t < 0 || t > 2 || c.icon_name[i] < 0) return fail(XWB_ERR_ARG, "xworld: bad icon_type / icon_name");
-        if (c.icon_name[i] + 1 > n_names[t]) n_names[t] = c.icon_name[i] + 1;
-    }
-    if (n_names[1] < 1 || n_names[2] < 1 || n_names[0] < 1)
-        return fail(XWB_ERR_ARG, "xworld: palette needs at least one goal, one block and one agent icon");
-    if (c.map_kind == XWB_MAP_NAV && c.num_goals > n_names[0])
-        return fail(XWB_ERR_ARG, "xworld: XWorldNav needs num_goals distinct goal names");
-    std::vector<int16_t> first, variants;
-    int off[3];
-    for (int t = 0; t < 3; ++t) {
-        off[t] = (int)first.size();
-        for (int nm = 0; nm < n_names[t]; ++nm) {
-            first.push_back((int16_t)variants.size());
-            int cnt = 0;
-            for (int i = 0; i < c.n_icons; ++i)
-                if (c.icon_type[i] == t && c.icon_name[i] == nm) { variants.push_back((int16_t)i); cnt++; }
-            if (cnt == 0) return fail(XWB_ERR_ARG, "xworld: name ids of a type must be dense");
-        }
-        first.push_back((int16_t)variants.size());
-    }
+    XWB_TRY(name_tables(c, names));
     // free cells / block capacity checks the reference leaves to Python asserts
     if (c.map_kind == XWB_MAP_NAV) {
         int X = c.dim % 2 == 0 ? c.dim - 1 : c.dim;
@@ -217,285 +228,302 @@ int xw_setup(xwb_sim *s) {
         int walls = std::min(c.num_blocks, c.dim) + std::min(std::max(c.num_blocks - c.dim, 0), c.dim - 1);
         if (c.num_goals + 1 + walls > c.dim * c.dim) return fail(XWB_ERR_ARG, "xworld: not enough free cells");
     }
-    // tile table: entry 0 = empty cell (canvas fill 255, xmap.cpp:129-132), entry i+1 = icon i
-    s->tile_table.assign((size_t)c.n_icons * ch * 144, 0);
-    build_tile_table(c.icons64, c.n_icons, ch, s->tile_table.data());
-    std::vector<uint8_t> atlas((size_t)(c.n_icons + 1) * ch * 144, 255);
-    memcpy(atlas.data() + (size_t)ch * 144, s->tile_table.data(), s->tile_table.size());
-    std::vector<uint8_t> types(c.n_icons);
-    std::vector<int16_t> names(c.n_icons);
-    for (int i = 0; i < c.n_icons; ++i) { types[i] = (uint8_t)c.icon_type[i]; names[i] = (int16_t)c.icon_name[i]; }
-    s->icon_type_h.assign(c.icon_type, c.icon_type + c.n_icons);
-    s->icon_name_h.assign(c.icon_name, c.icon_name + c.n_icons);
-    s->icon_colored_h.assign(c.n_icons, 0);
-    if (c.icon_colored) s->icon_colored_h.assign(c.icon_colored, c.icon_colored + c.n_icons);
+    return XWB_OK;
+}
 
-    int rc;
-    if ((rc = dev_alloc(s, &s->d_grid, (size_t)n * cells))) return rc;
-    if ((rc = dev_alloc(s, &s->d_agent, n))) return rc;
-    if ((rc = dev_alloc(s, &s->d_task_steps, n))) return rc;
-    if ((rc = dev_alloc(s, &s->d_task_state, n))) return rc;
+// the scalar parameters: what the kernels need to know of the configuration
+void xw_fill_scalars(xwb_sim *s, const NameTables &names) {
+    const xwb_config &c = s->cfg;
+    XwParams &p = s->xw;
+    p.n = s->n; p.context = c.context; p.max_steps = c.max_steps; p.act_rep = 1;
+    p.map_kind = c.map_kind; p.max_dim = c.max_dim; p.dim = c.dim;
+    // under the curriculum the levels place 2 or 4 goals whatever cfg.num_goals says (XWorldNav.py:27-34): the per-env
+    // goal-image cache and every kernel that indexes it use the levels' maximum
+    p.num_goals = curriculum_cfg(c) ? 4 : c.num_goals;
+    p.num_blocks = c.num_blocks; p.max_steps_factor = c.max_steps_factor; p.task_mode = c.task_mode;
+    p.channels = c.color ? 3 : 1; p.n_icons = c.n_icons;
+    p.obs_f32 = c.obs_format == XWB_OBS_F32 ? 1 : 0;
+    p.curriculum = curriculum_cfg(c) ? c.curriculum : 0.0;
+    p.visible_radius = c.visible_radius; p.out_dim = s->out_h; p.no_wall_shadow = c.no_wall_shadow;
+    p.n_tasks = c.n_tasks; p.group2d = group2d_cfg(c.tasks, c.n_tasks);
+    p.task_weighted = c.task_schedule == XWB_SCHEDULE_WEIGHTED;
+    p.n_tasks2 = c.n_tasks2; p.group2d_2 = group2d_cfg(c.tasks2, c.n_tasks2);
+    p.task_weighted2 = c.task_schedule2 == XWB_SCHEDULE_WEIGHTED;
+    for (int i = 0; i < 8; ++i) {
+        p.tasks[i] = i < c.n_tasks ? c.tasks[i] : 0;
+        p.tasks2[i] = i < c.n_tasks2 ? c.tasks2[i] : 0;
+        p.task_acc[i] = (i ? p.task_acc[i - 1] : 0.0) + (i < c.n_tasks && p.task_weighted ? c.task_weights[i] : 0.0);
+        p.task_acc2[i] = (i ? p.task_acc2[i - 1] : 0.0) + (i < c.n_tasks2 && p.task_weighted2 ? c.task_weights2[i] : 0.0);
+    }
+    p.exclusive = exclusive_cfg(c) ? 1 : 0;
+    p.group_weight[0] = c.task_group_weight; p.group_weight[1] = c.task_group_weight2;
+    p.policy_seed = c.policy_seed; p.env_gid0 = c.env_gid0; p.seed = c.seed;
+    for (int t = 0; t < 3; ++t) { p.n_names[t] = names.n_names[t]; p.name_first_off[t] = names.off[t]; }
+    p.name_first_len = (int)names.first.size(); p.name_variants_len = (int)names.variants.size();
+    p.wait_slot = SYNC_RESET;
+}
+
+// s->xw's copies of the buffers all three games share (xwb_create made them).  obs and packed are not here: the caller can
+// move them between calls (xwb_bind_obs, the results ring), so xw_params fills them in per launch.
+void xw_bind_shared(xwb_sim *s) {
+    XwParams &p = s->xw;
+    p.actions_out = s->d_actions; p.num_steps = s->d_num_steps; p.episode = s->d_episode; p.success = s->d_success;
+    p.reward = s->d_reward; p.done = s->d_done; p.err_count = s->d_err; p.minstd = s->d_minstd;
+}
+
+// the live state, then the pre-generated next episodes and the look-ahead snapshots where the configuration allows them
+int xw_alloc_state(xwb_sim *s) {
+    const xwb_config &c = s->cfg;
+    XwParams &p = s->xw;
+    const size_t n = (size_t)s->n, cells = (size_t)c.max_dim * c.max_dim;
+    const bool exclusive2 = p.exclusive && c.n_tasks2 > 0;
+    XWB_TRY(dev_alloc(s, &p.grid, n * cells));
+    XWB_TRY(dev_alloc(s, &p.agent_xy, n));
+    XWB_TRY(dev_alloc(s, &p.task_steps, n));
+    XWB_TRY(dev_alloc(s, &p.task_state, n));
     if (c.n_tasks2 > 0) {
-        if ((rc = dev_alloc(s, &s->d_task_state2, n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_task_steps2, n))) return rc;
+        XWB_TRY(dev_alloc(s, &p.task_state2, n)); XWB_TRY(dev_alloc(s, &p.task_steps2, n));
     }
-    // simulator_interface.cpp:46-48: lang_acquisition runs the groups non-exclusively whatever the flag says
-    const bool exclusive = c.task_groups_exclusive && c.task_mode != XWB_TASKMODE_LANG_ACQ;
-    if (exclusive && c.n_tasks2 > 0) {
-        if ((rc = dev_alloc(s, &s->d_grp_order, n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_idle_list, n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_idle_count, 3))) return rc;
+    if (exclusive2) {
+        XWB_TRY(dev_alloc(s, &p.grp_order, n));
+        XWB_TRY(dev_alloc(s, &p.idle_list, n)); XWB_TRY(dev_alloc(s, &p.idle_count, 3));
     }
-    if ((rc = dev_alloc(s, &s->d_perf, 40))) return rc;
+    XWB_TRY(dev_alloc(s, &p.perf, 40));
     // Pre-generated next episodes: possible where an env's next episode is a pure function of (seed, global id, episode + 1)
     // and the render reads nothing but the grid -- full observation, no curriculum (the level depends on the results so far),
     // no per-env reference engine (its state depends on the draws so far), no exclusive group order carried across resets.
     // (float32 frames stay on the classic paths: their plain whole-batch render variant measured 5-8 % slower than the
     // variants the classic paths use -- 416 vs 385 / 394 us on the C4-sized batch)
-    s->pregen = c.visible_radius == 0 && !curriculum_cfg(c) && c.rng_mode != XWB_RNG_MINSTD && !(exclusive && c.n_tasks2 > 0) &&
+    s->pregen = c.visible_radius == 0 && !curriculum_cfg(c) && c.rng_mode != XWB_RNG_MINSTD && !exclusive2 &&
                 c.obs_format == XWB_OBS_U8 && !(c.debug_flags & XWB_DEBUG_NO_PREGEN);
     if (s->pregen) {
-        if ((rc = dev_alloc(s, &s->d_sh_ep, n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_sh_grid, (size_t)2 * n * cells))) return rc;           // two slots per env
-        if ((rc = dev_alloc(s, &s->d_sh_agent, (size_t)2 * n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_sh_task_state, (size_t)2 * n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_sh_task_state2, (size_t)2 * n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_sh_sent_names, (size_t)2 * n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_sh_cand2d, (size_t)2 * n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_sh_goal_cells, (size_t)2 * n * XW_MAX_GOALS))) return rc;
+        XWB_TRY(dev_alloc(s, &p.sh_ep, n));
+        XWB_TRY(dev_alloc(s, &p.sh_grid, 2 * n * cells));                      // two slots per env
+        XWB_TRY(dev_alloc(s, &p.sh_agent_xy, 2 * n));
+        XWB_TRY(dev_alloc(s, &p.sh_task_state, 2 * n)); XWB_TRY(dev_alloc(s, &p.sh_task_state2, 2 * n));
+        XWB_TRY(dev_alloc(s, &p.sh_sent_names, 2 * n)); XWB_TRY(dev_alloc(s, &p.sh_cand2d, 2 * n));
+        XWB_TRY(dev_alloc(s, &p.sh_goal_cells, 2 * n * XW_MAX_GOALS));
         // the default loop's xwb_step as ONE launch (XwParams::snap_*): frames without a context ring only
         if (c.context == 1 && !(c.debug_flags & XWB_DEBUG_NO_FUSED))
-            for (int k = 0; k < 2; ++k) {
-                if ((rc = dev_alloc(s, &s->d_snap_grid[k], (size_t)n * cells))) return rc;
-            }
+            for (int k = 0; k < 2; ++k) XWB_TRY(dev_alloc(s, &s->d_snap_grid[k], n * cells));
     }
-    if ((rc = dev_alloc(s, &s->d_done_list, (size_t)2 * n))) return rc;       // two lists, three counters: xwb_sim.h count_sel
-    if ((rc = dev_alloc(s, &s->d_done_ep, (size_t)2 * n))) return rc;
-    if ((rc = dev_alloc(s, &s->d_done_count, 3))) return rc;
-    if ((rc = dev_alloc(s, &s->d_fresh, n))) return rc;
-    if ((rc = dev_alloc(s, &s->d_icon_type, ((size_t)c.n_icons + 3) & ~(size_t)3))) return rc;   // the step kernel stages it dword-wise
-    if ((rc = dev_alloc(s, &s->d_icon_colored, c.n_icons))) return rc;
-    if ((rc = dev_alloc(s, &s->d_goal_cells, (size_t)n * XW_MAX_GOALS, 0xff))) return rc;
-    if ((rc = dev_alloc(s, &s->d_cand2d, n))) return rc;
-    if ((rc = dev_alloc(s, &s->d_sent_names, n, 0xff))) return rc;
-    const bool curriculum = c.curriculum != 0 && c.map_kind == XWB_MAP_NAV;       // XWorldWalls never reads the flag
-    // under the curriculum the levels place 2 or 4 goals whatever cfg.num_goals says (XWorldNav.py:27-34): the per-env
-    // goal-image cache and every kernel that indexes it use the levels' maximum
-    const int img_goals = curriculum ? 4 : c.num_goals;
-    if (curriculum) {
-        if ((rc = dev_alloc(s, &s->d_cur_level, n, c.start_level))) return rc;
-        if ((rc = dev_alloc(s, &s->d_cur_counter, n))) return rc;
-        if ((rc = dev_alloc(s, &s->d_cur_usage, (size_t)n * 9 * XW_USAGE_BYTES))) return rc;
+    XWB_TRY(dev_alloc(s, &p.done_list, 2 * n));                                // two lists, three counters: xwb_sim.h count_sel
+    XWB_TRY(dev_alloc(s, &p.done_ep, 2 * n));
+    XWB_TRY(dev_alloc(s, &p.done_count, 3));
+    XWB_TRY(dev_alloc(s, &p.fresh, n));
+    XWB_TRY(dev_alloc(s, &p.goal_cells, n * XW_MAX_GOALS, 0xff));
+    XWB_TRY(dev_alloc(s, &p.cand2d, n));
+    XWB_TRY(dev_alloc(s, &p.sent_names, n, 0xff));
+    if (curriculum_cfg(c)) {
+        XWB_TRY(dev_alloc(s, &p.cur_level, n, c.start_level));
+        XWB_TRY(dev_alloc(s, &p.cur_counter, n)); XWB_TRY(dev_alloc(s, &p.cur_usage, n * 9 * XW_USAGE_BYTES));
     }
-    if ((rc = dev_alloc(s, &s->d_sync, 16))) return rc;
-    if ((rc = dev_alloc(s, &s->d_term_grid, (size_t)n * cells))) return rc;
-    if ((rc = dev_alloc(s, &s->d_term_flag, n))) return rc;
-    if ((rc = dev_alloc(s, &s->d_agent_dir, n, 1))) return rc;                 // heading "down": yaw 1.5707963
-    if (c.visible_radius > 0) {
-        if ((rc = dev_alloc(s, &s->d_goal_warp, (size_t)n * XW_MAX_GOALS * 6))) return rc;
-        if ((rc = dev_alloc(s, &s->d_goal_img, (size_t)n * img_goals * 4096))) return rc;
-        const size_t npx = (size_t)c.n_icons * 64 * 64;
-        std::vector<uint8_t> a4((npx + 2) * 4, 0);
-        for (size_t i = 0; i < npx; ++i) for (int k = 0; k < 3; ++k) a4[i * 4 + k] = c.icons64[i * 3 + k];
-        for (int k = 0; k < 3; ++k) a4[npx * 4 + k] = 255;            // white pixel, then a black one
-        // XItem::get_item_image turns the agent's icon by 90 - yaw degrees about (32, 32) with a white border: the three
-        // quarter turns are exact integer maps (source index 64 falls outside): heading right, left, up
-        std::vector<uint32_t> rot_off(c.n_icons, 0);
-        for (int ic = 0; ic < c.n_icons; ++ic) {
-            if (c.icon_type[ic] != XWB_ICON_AGENT) continue;
-            rot_off[ic] = (uint32_t)(a4.size() / 4);
-            for (int h = 0; h < 3; ++h)
-                for (int py = 0; py < 64; ++py)
-                    for (int px = 0; px < 64; ++px) {
-                        const int ix = h == 0 ? 64 - py : (h == 1 ? py : 64 - px), iy = h == 0 ? px : (h == 1 ? 64 - px : 64 - py);
-                        const bool in = ix >= 0 && ix < 64 && iy >= 0 && iy < 64;
-                        for (int k = 0; k < 3; ++k) a4.push_back(in ? c.icons64[(((size_t)ic * 64 + iy) * 64 + ix) * 3 + k] : 255);
-                        a4.push_back(0);
-                    }
-        }
-        if ((rc = dev_alloc(s, &s->d_atlas64, a4.size()))) return rc;
-        HIP_TRY(hipMemcpy(s->d_atlas64, a4.data(), a4.size(), hipMemcpyHostToDevice));
-        if ((rc = dev_alloc(s, &s->d_agent_rot, (size_t)c.n_icons))) return rc;
-        HIP_TRY(hipMemcpy(s->d_agent_rot, rot_off.data(), rot_off.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(xw_ego_tables(c.visible_radius, c.max_dim, s->out_h, &s->d_ego_taps, &s->xw.ego_fast, &s->ego_cell_edge, &s->xw.ego_span));
-        s->allocs.push_back(s->d_ego_taps);
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_view, hipEventDisableTiming | hipEventDisableSystemFence));
-    } else {
-        // xwb_xw_render_view gathers whole 16-byte pieces from the item images as the view stores them: 3 bytes per pixel
-        const size_t cell = 64 * 64 * 3;
-        std::vector<uint8_t> a3((size_t)(c.n_icons + 1) * cell, 255);
-        memcpy(a3.data() + cell, c.icons64, (size_t)c.n_icons * cell);
-        if ((rc = dev_alloc(s, &s->d_view_atlas, a3.size()))) return rc;
-        HIP_TRY(hipMemcpy(s->d_view_atlas, a3.data(), a3.size(), hipMemcpyHostToDevice));
+    XWB_TRY(dev_alloc(s, &p.term_grid, n * cells)); XWB_TRY(dev_alloc(s, &p.term_flag, n));
+    XWB_TRY(dev_alloc(s, &p.agent_dir, n, 1));                                 // heading "down": yaw 1.5707963
+    return XWB_OK;
+}
+
+// the palette: host copies for the getters, the icon and name tables, the 12-px tile table the full-observation render and the
+// egocentric frame's consumers read, and under full observation the 64-px images of xwb_xw_render_view
+int xw_upload_palette(xwb_sim *s, const NameTables &names) {
+    const xwb_config &c = s->cfg;
+    XwParams &p = s->xw;
+    const size_t ni = (size_t)c.n_icons;
+    s->icon_type_h.assign(c.icon_type, c.icon_type + ni);
+    s->icon_name_h.assign(c.icon_name, c.icon_name + ni);
+    s->icon_colored_h.assign(ni, 0);
+    if (c.icon_colored) s->icon_colored_h.assign(c.icon_colored, c.icon_colored + ni);
+    std::vector<uint8_t> types(ni), colored(ni);
+    std::vector<int16_t> name_ids(ni);
+    for (size_t i = 0; i < ni; ++i) {
+        types[i] = (uint8_t)c.icon_type[i]; name_ids[i] = (int16_t)c.icon_name[i]; colored[i] = s->icon_colored_h[i] ? 1 : 0;
     }
-    if ((rc = dev_alloc(s, &s->d_icon_name, c.n_icons))) return rc;
-    if ((rc = dev_alloc(s, &s->d_name_first, first.size()))) return rc;
-    if ((rc = dev_alloc(s, &s->d_name_variants, variants.size()))) return rc;
-    const bool f32 = c.obs_format == XWB_OBS_F32;
-    if ((rc = dev_alloc(s, &s->d_atlas, f32 ? atlas.size() : atlas.size() / 4))) return rc;
-    HIP_TRY(hipMemcpy(s->d_icon_type, types.data(), types.size(), hipMemcpyHostToDevice));
-    if (c.icon_colored) {
-        std::vector<uint8_t> col(c.n_icons);
-        for (int i = 0; i < c.n_icons; ++i) col[i] = c.icon_colored[i] ? 1 : 0;
-        HIP_TRY(hipMemcpy(s->d_icon_colored, col.data(), col.size(), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(s->d_icon_name, names.data(), names.size() * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_name_first, first.data(), first.size() * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_name_variants, variants.data(), variants.size() * 2, hipMemcpyHostToDevice));
-    if (f32) {
+    XWB_TRY(dev_upload(s, &p.icon_type, types, (ni + 3) & ~(size_t)3));        // the step kernel stages it dword-wise
+    XWB_TRY(dev_upload(s, &p.icon_colored, colored));
+    XWB_TRY(dev_upload(s, &p.icon_name, name_ids));
+    XWB_TRY(dev_upload(s, &p.name_first, names.first));
+    XWB_TRY(dev_upload(s, &p.name_variants, names.variants));
+    // tile table: entry 0 = empty cell (canvas fill 255, xmap.cpp:129-132), entry i+1 = icon i
+    const size_t tile = (size_t)p.channels * 144;
+    s->tile_table.assign(ni * tile, 0);
+    build_tile_table(c.icons64, c.n_icons, p.channels, s->tile_table.data());
+    std::vector<uint8_t> atlas((ni + 1) * tile, 255);
+    memcpy(atlas.data() + tile, s->tile_table.data(), s->tile_table.size());
+    if (p.obs_f32) {
         // py_simulator.cpp:262-272: `float scale = 1 / 255.0` then pixel * scale, a float32 product
         std::vector<float> af(atlas.size());
         const float scale = (float)(1 / 255.0);
         for (size_t i = 0; i < atlas.size(); ++i) af[i] = (float)atlas[i] * scale;
-        HIP_TRY(hipMemcpy(s->d_atlas, af.data(), af.size() * 4, hipMemcpyHostToDevice));
+        XWB_TRY(dev_upload(s, &p.atlas, af));
     } else {
-        HIP_TRY(hipMemcpy(s->d_atlas, atlas.data(), atlas.size(), hipMemcpyHostToDevice));
+        XWB_TRY(dev_upload(s, &p.atlas, atlas));
     }
+    if (c.visible_radius == 0) {
+        // xwb_xw_render_view gathers whole 16-byte pieces from the item images as the view stores them: 3 bytes per pixel
+        const size_t cell = 64 * 64 * 3;
+        std::vector<uint8_t> a3((ni + 1) * cell, 255);
+        memcpy(a3.data() + cell, c.icons64, ni * cell);
+        XWB_TRY(dev_upload(s, &s->d_view_atlas, a3));
+    }
+    return XWB_OK;
+}
+
+// the internal queue, the events and sync words of its hand-overs with the caller's queue, the watchdog's poison word
+int xw_queue_objects(xwb_sim *s) {
     // (a high-priority side queue was tried: no gain beside the renders, and batches created after another one in the same
     // process then failed their resume tests -- left at the default priority)
     HIP_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_step, hipEventDisableTiming | hipEventDisableSystemFence));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_reset, hipEventDisableTiming | hipEventDisableSystemFence));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_term, hipEventDisableTiming | hipEventDisableSystemFence));
-    HIP_TRY(hipEventCreateWithFlags(&s->ev_cells, hipEventDisableTiming | hipEventDisableSystemFence));
+    for (hipEvent_t *ev : {&s->ev_step, &s->ev_reset, &s->ev_term, &s->ev_cells})
+        HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming | hipEventDisableSystemFence));
+    XWB_TRY(dev_alloc(s, &s->xw.sync, 16));
+    // the watchdog's host-visible word (read at the top of every verb, no sync)
+    void *hp = nullptr, *dp = nullptr;
+    HIP_TRY(hipHostMalloc(&hp, 64, hipHostMallocMapped));
+    memset(hp, 0, 64);
+    s->h_poison = static_cast<uint32_t *>(hp);
+    HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
+    s->xw.poison_host = static_cast<uint32_t *>(dp);
+    return XWB_OK;
+}
 
+// the 64-px images the egocentric render samples: 4 bytes per pixel, one white and one black pixel behind the icons, then
+// the turned copies of the agent icons (rot_off: where each agent icon's copies start)
+void ego_atlas64(const xwb_config &c, std::vector<uint8_t> &a4, std::vector<uint32_t> &rot_off) {
+    const size_t npx = (size_t)c.n_icons * 64 * 64;
+    a4.assign((npx + 2) * 4, 0);
+    for (size_t i = 0; i < npx; ++i) for (int k = 0; k < 3; ++k) a4[i * 4 + k] = c.icons64[i * 3 + k];
+    for (int k = 0; k < 3; ++k) a4[npx * 4 + k] = 255;            // white pixel, then a black one
+    // XItem::get_item_image turns the agent's icon by 90 - yaw degrees about (32, 32) with a white border: the three
+    // quarter turns are exact integer maps (source index 64 falls outside): heading right, left, up
+    rot_off.assign(c.n_icons, 0);
+    for (int ic = 0; ic < c.n_icons; ++ic) {
+        if (c.icon_type[ic] != XWB_ICON_AGENT) continue;
+        rot_off[ic] = (uint32_t)(a4.size() / 4);
+        for (int h = 0; h < 3; ++h)
+            for (int py = 0; py < 64; ++py)
+                for (int px = 0; px < 64; ++px) {
+                    const int ix = h == 0 ? 64 - py : (h == 1 ? py : 64 - px), iy = h == 0 ? px : (h == 1 ? 64 - px : 64 - py);
+                    const bool in = ix >= 0 && ix < 64 && iy >= 0 && iy < 64;
+                    for (int k = 0; k < 3; ++k) a4.push_back(in ? c.icons64[(((size_t)ic * 64 + iy) * 64 + ix) * 3 + k] : 255);
+                    a4.push_back(0);
+                }
+    }
+}
+
+// The goal-cell cache of the egocentric render, [env][goal slot][view cell][heading]: ~340 KB per env at r = 3 (11 GB for a
+// C4-sized batch; the GPU has 288 GB).  Taken only if it leaves at least half of the free memory to the caller; without it
+// (p.ego_cache stays null) every goal cell is evaluated every frame.
+int ego_cache_alloc(xwb_sim *s) {
     XwParams &p = s->xw;
-    p.n = n; p.context = c.context; p.max_steps = c.max_steps; p.act_rep = 1; p.auto_reset = 0;
-    p.map_kind = c.map_kind; p.max_dim = c.max_dim; p.dim = c.dim; p.num_goals = img_goals;
-    p.num_blocks = c.num_blocks; p.max_steps_factor = c.max_steps_factor; p.task_mode = c.task_mode;
-    p.channels = ch; p.n_icons = c.n_icons;
-    p.obs_f32 = f32 ? 1 : 0;
-    p.n_tasks = c.n_tasks;
-    p.group2d = c.n_tasks > 0 && c.tasks[0] >= XWB_TASK2D_TARGET;
-    p.curriculum = curriculum ? c.curriculum : 0.0; p.cur_level = s->d_cur_level; p.cur_counter = s->d_cur_counter; p.cur_usage = s->d_cur_usage;
-    p.sync = s->d_sync; p.sig_epoch = 0; p.wait_epoch = 0;
-    {   // the watchdog's host-visible word (read at the top of every verb, no sync)
-        void *hp = nullptr, *dp = nullptr;
-        HIP_TRY(hipHostMalloc(&hp, 64, hipHostMallocMapped));
-        memset(hp, 0, 64);
-        s->h_poison = static_cast<uint32_t *>(hp);
-        HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
-        p.poison_host = static_cast<uint32_t *>(dp);
-    }
-    p.minstd = s->d_minstd;
-    p.sent_names = s->d_sent_names; p.term_grid = s->d_term_grid; p.term_flag = s->d_term_flag;
-    p.goal_cells = s->d_goal_cells; p.cand2d = s->d_cand2d; p.icon_colored = s->d_icon_colored;
-    p.visible_radius = c.visible_radius; p.out_dim = s->out_h; p.no_wall_shadow = c.no_wall_shadow;
-    p.agent_dir = s->d_agent_dir; p.goal_warp = s->d_goal_warp; p.atlas64 = s->d_atlas64; p.ego_taps = s->d_ego_taps; p.goal_img = s->d_goal_img; p.ego_agent_rot = s->d_agent_rot;
-    for (int i = 0; i < 8; ++i) p.tasks[i] = i < c.n_tasks ? c.tasks[i] : 0;
-    p.task_weighted = c.task_schedule == XWB_SCHEDULE_WEIGHTED;
-    p.n_tasks2 = c.n_tasks2;
-    p.group2d_2 = c.n_tasks2 > 0 && c.tasks2[0] >= XWB_TASK2D_TARGET;
-    p.task_weighted2 = c.task_schedule2 == XWB_SCHEDULE_WEIGHTED;
-    for (int i = 0; i < 8; ++i) p.tasks2[i] = i < c.n_tasks2 ? c.tasks2[i] : 0;
-    for (int i = 0; i < 8; ++i) p.task_acc2[i] = (i ? p.task_acc2[i - 1] : 0.0) + (i < c.n_tasks2 && p.task_weighted2 ? c.task_weights2[i] : 0.0);
-    p.task_state2 = s->d_task_state2; p.task_steps2 = s->d_task_steps2;
-    p.perf = s->d_perf;
-    p.shadow = 0; p.swap_shadow = 0; p.list_swap = 0; p.regen_wait = 0; p.wait_slot = SYNC_RESET; p.sh_ep = s->d_sh_ep;
-    p.sh_grid = s->d_sh_grid; p.sh_agent_xy = s->d_sh_agent; p.sh_task_state = s->d_sh_task_state; p.sh_task_state2 = s->d_sh_task_state2;
-    p.sh_sent_names = s->d_sh_sent_names; p.sh_cand2d = s->d_sh_cand2d; p.sh_goal_cells = s->d_sh_goal_cells;
-    p.exclusive = exclusive ? 1 : 0;
-    p.group_weight[0] = c.task_group_weight; p.group_weight[1] = c.task_group_weight2;
-    p.grp_order = s->d_grp_order; p.idle_list = s->d_idle_list; p.idle_count = s->d_idle_count; p.idle_count_next = nullptr;
-    for (int i = 0; i < 8; ++i) p.task_acc[i] = (i ? p.task_acc[i - 1] : 0.0) + (i < c.n_tasks && p.task_weighted ? c.task_weights[i] : 0.0);
-    p.policy_seed = c.policy_seed; p.env_gid0 = c.env_gid0; p.policy_step = 0; p.seed = c.seed;
-    p.icon_type = s->d_icon_type; p.icon_name = s->d_icon_name;
-    p.name_first = s->d_name_first; p.name_variants = s->d_name_variants;
-    for (int t = 0; t < 3; ++t) { p.n_names[t] = n_names[t]; p.name_first_off[t] = off[t]; }
-    p.name_first_len = (int)first.size(); p.name_variants_len = (int)variants.size();
-    p.atlas = s->d_atlas;
-    p.actions = nullptr; p.mask = nullptr; p.actions_out = s->d_actions;
-    p.grid = s->d_grid; p.agent_xy = s->d_agent; p.task_steps = s->d_task_steps; p.task_state = s->d_task_state;
-    p.num_steps = s->d_num_steps; p.episode = s->d_episode; p.success = s->d_success; p.fresh = s->d_fresh;
-    p.reward = s->d_reward; p.done = s->d_done; p.obs = static_cast<uint8_t *>(s->d_obs);
-    p.packed = nullptr;                     // set per call (xw_params)
-    p.done_list = s->d_done_list; p.done_ep = s->d_done_ep; p.done_count = s->d_done_count; p.done_count_next = s->d_done_count + 1;
-    p.err_count = s->d_err;
-    if (c.visible_radius > 0) {
-        if ((rc = dev_alloc(s, &s->d_ego_tab, xw_ego_tab_bytes(p)))) return rc;
-        p.ego_tab = s->d_ego_tab;
-        p.ego_cache = nullptr; p.ego_cache_valid = nullptr; p.ego_cache_entry = 0; p.ego_cache_words = 0;
-        p.ego_cellinfo = nullptr; p.ego_miss = nullptr; p.ego_miss_count = nullptr; p.ego_xtab = nullptr; p.ego_clsimg = nullptr; p.ego_tab3 = nullptr; p.ego_cellsrc = nullptr;
-        p.ego_cellsrc_list = nullptr; p.ego_miss_list = nullptr; p.ego_miss_count_list = nullptr;
-        if (p.ego_fast && !(c.debug_flags & XWB_DEBUG_EGO_NO_CACHE)) {
-            // rendered goal cells, [env][goal slot][view cell][heading]: ~340 KB per env at r = 3 (11 GB for a C4-sized batch;
-            // the GPU has 288 GB).  Taken only if it leaves at least half of the free memory to the caller.
-            size_t entry = xw_ego_cache_entry_bytes(p, s->ego_cell_edge);
-            if (p.ego_span && xw_ego_square_entry_bytes(p) > entry) entry = xw_ego_square_entry_bytes(p);   // (the span path's layout)
-            const size_t per_env = (size_t)p.num_goals * c.visible_radius * c.visible_radius * 4;
-            const size_t bytes = (size_t)n * per_env * entry;
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes < free_b / 2 && (per_env + 31) / 32 <= 64) {
-                void *q = nullptr;
-                if (hipMalloc(&q, bytes) == hipSuccess) {
-                    s->allocs.push_back(q);
-                    s->d_ego_cache = static_cast<uint8_t *>(q);
-                    const size_t words = (per_env + 31) / 32;
-                    if ((rc = dev_alloc(s, &s->d_ego_cache_valid, (size_t)n * words))) return rc;
-                    p.ego_cache = s->d_ego_cache; p.ego_cache_valid = s->d_ego_cache_valid;
-                    p.ego_cache_entry = (uint32_t)entry; p.ego_cache_words = (uint32_t)words;
-                    // span path: classes of the images every env shares (everything but goals)
-                    std::vector<uint8_t> cls((size_t)c.n_icons + 2, 0xff);
-                    std::vector<uint16_t> cls_icon;
-                    for (int i = 0; i < c.n_icons + 2; ++i)
-                        if (i >= c.n_icons || c.icon_type[i] != 0) { cls[i] = (uint8_t)(cls_icon.size() < 255 ? cls_icon.size() : 0); cls_icon.push_back((uint16_t)i); }
-                    if (p.ego_span && !(c.debug_flags & XWB_DEBUG_EGO_NO_SPAN) && p.n_icons < 8000 && cls_icon.size() <= 16 &&
-                        (p.ego_ncls = (int)cls_icon.size(), xw_ego_square_tab_bytes(p) <= ((size_t)1 << 27))) {   // (its offsets are 23 bits of 16-byte units)
-                        const int rr = c.visible_radius * c.visible_radius;
-                        if ((rc = dev_alloc(s, &s->d_ego_cellinfo, (size_t)n * rr))) return rc;
-                        if ((rc = dev_alloc(s, &s->d_ego_cellsrc, (size_t)n * rr))) return rc;
-                        p.ego_cellsrc = s->d_ego_cellsrc;
-                        if ((rc = dev_alloc(s, &s->d_ego_cellsrc_list, (size_t)n * rr))) return rc;
-                        if ((rc = dev_alloc(s, &s->d_ego_miss_list, (size_t)n * (p.num_goals < rr ? p.num_goals : rr)))) return rc;
-                        if ((rc = dev_alloc(s, &s->d_ego_miss_count_list, 4))) return rc;
-                        p.ego_cellsrc_list = s->d_ego_cellsrc_list; p.ego_miss_list = s->d_ego_miss_list; p.ego_miss_count_list = s->d_ego_miss_count_list;
-                        if ((rc = dev_alloc(s, &s->d_ego_miss, (size_t)n * (p.num_goals < rr ? p.num_goals : rr)))) return rc;
-                        if ((rc = dev_alloc(s, &s->d_ego_miss_count, 4))) return rc;
-                        if ((rc = dev_alloc(s, &s->d_ego_cls, cls.size()))) return rc;
-                        if ((rc = dev_alloc(s, &s->d_ego_cls_icon, cls_icon.size()))) return rc;
-                        HIP_TRY(hipMemcpy(s->d_ego_cls, cls.data(), cls.size(), hipMemcpyHostToDevice));
-                        HIP_TRY(hipMemcpy(s->d_ego_cls_icon, cls_icon.data(), cls_icon.size() * 2, hipMemcpyHostToDevice));
-                        p.ego_cls = s->d_ego_cls; p.ego_cls_icon = s->d_ego_cls_icon; p.ego_ncls = (int)cls_icon.size();
-                        if ((rc = dev_alloc(s, &s->d_ego_tab3, xw_ego_square_tab_bytes(p) + 16))) return rc;
-                        p.ego_tab3 = s->d_ego_tab3;
-                        if ((rc = dev_alloc(s, &s->d_ego_xtab, xw_ego_xtab_bytes(p) / sizeof(uint32_t)))) return rc;
-                        if ((rc = dev_alloc(s, &s->d_ego_clsimg, (size_t)4 * 16))) return rc;
-                        p.ego_xtab = s->d_ego_xtab; p.ego_clsimg = s->d_ego_clsimg;
-                        p.ego_cellinfo = s->d_ego_cellinfo; p.ego_miss = s->d_ego_miss; p.ego_miss_count = s->d_ego_miss_count;
-                    }
-                } else {
-                    (void)hipGetLastError();
+    const int r = p.visible_radius;
+    size_t entry = xw_ego_cache_entry_bytes(p, s->ego_cell_edge);
+    if (p.ego_span && xw_ego_square_entry_bytes(p) > entry) entry = xw_ego_square_entry_bytes(p);   // (the span path's layout)
+    const size_t per_env = (size_t)p.num_goals * r * r * 4, words = (per_env + 31) / 32;
+    const size_t bytes = (size_t)p.n * per_env * entry;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes >= free_b / 2 || words > 64) return XWB_OK;
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return XWB_OK; }
+    s->allocs.push_back(q);
+    p.ego_cache = static_cast<uint8_t *>(q);
+    XWB_TRY(dev_alloc(s, &p.ego_cache_valid, (size_t)p.n * words));
+    p.ego_cache_entry = (uint32_t)entry; p.ego_cache_words = (uint32_t)words;
+    return XWB_OK;
+}
+
+// The span path's tables (kernels_xworld_ego_span.hip), where the geometry and the palette allow the path: it reads the cache.
+// Leaves p.ego_cellinfo null otherwise.
+int ego_span_alloc(xwb_sim *s) {
+    const xwb_config &c = s->cfg;
+    XwParams &p = s->xw;
+    // classes of the images every env shares (everything but goals)
+    std::vector<uint8_t> cls((size_t)c.n_icons + 2, 0xff);
+    std::vector<uint16_t> cls_icon;
+    for (int i = 0; i < c.n_icons + 2; ++i)
+        if (i >= c.n_icons || c.icon_type[i] != 0) { cls[i] = (uint8_t)(cls_icon.size() < 255 ? cls_icon.size() : 0); cls_icon.push_back((uint16_t)i); }
+    if (!p.ego_span || (c.debug_flags & XWB_DEBUG_EGO_NO_SPAN) || p.n_icons >= 8000 || cls_icon.size() > 16) return XWB_OK;
+    p.ego_ncls = (int)cls_icon.size();                                          // (the sizes below depend on it)
+    if (xw_ego_square_tab_bytes(p) > ((size_t)1 << 27)) return XWB_OK;          // (its offsets are 23 bits of 16-byte units)
+    const size_t rr = (size_t)c.visible_radius * c.visible_radius, n = (size_t)p.n;
+    const size_t misses = n * ((size_t)p.num_goals < rr ? (size_t)p.num_goals : rr);
+    XWB_TRY(dev_alloc(s, &p.ego_cellinfo, n * rr));
+    XWB_TRY(dev_alloc(s, &p.ego_cellsrc, n * rr));
+    XWB_TRY(dev_alloc(s, &p.ego_cellsrc_list, n * rr));
+    XWB_TRY(dev_alloc(s, &p.ego_miss_list, misses)); XWB_TRY(dev_alloc(s, &p.ego_miss_count_list, 4));
+    XWB_TRY(dev_alloc(s, &p.ego_miss, misses)); XWB_TRY(dev_alloc(s, &p.ego_miss_count, 4));
+    XWB_TRY(dev_upload(s, &p.ego_cls, cls));
+    XWB_TRY(dev_upload(s, &p.ego_cls_icon, cls_icon));
+    XWB_TRY(dev_alloc(s, &p.ego_tab3, xw_ego_square_tab_bytes(p) + 16));       // these three: filled by launch_xw_ego_build_squares
+    XWB_TRY(dev_alloc(s, &p.ego_xtab, xw_ego_xtab_bytes(p) / sizeof(uint32_t)));
+    XWB_TRY(dev_alloc(s, &p.ego_clsimg, (size_t)4 * 16));
+    return XWB_OK;
+}
+
+// Which squares of the span path's table are one flat colour (empty cells: 255; outside the map / shadow: 0): found by looking
+// at the table itself, so the shortcut the gather takes for them (XwParams::ego_flat) cannot change a byte
+int ego_flat_scan(xwb_sim *s) {
+    const xwb_config &c = s->cfg;
+    XwParams &p = s->xw;
+    const int r = c.visible_radius, U = ego_square(r).U, UP = ego_square(r).UP, RR = r * r, nc = p.ego_ncls;
+    const size_t CBP = (size_t)ego_square(r).plane, PBP = (size_t)RR * CBP, keys = (size_t)4 * nc * nc * nc;
+    std::vector<uint8_t> tab(xw_ego_square_tab_bytes(p)), flat(keys * RR, 0);
+    HIP_TRY(hipMemcpy(tab.data(), p.ego_tab3, tab.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < keys; ++k)
+        for (int f = 0; f < RR; ++f) {
+            const uint8_t v0 = tab[k * p.channels * PBP + (size_t)f * CBP];
+            bool same = v0 == 0 || v0 == 255;
+            for (int chn = 0; chn < p.channels && same; ++chn)
+                for (int y = 0; y < U && same; ++y) {
+                    const uint8_t *row = tab.data() + (k * p.channels + chn) * PBP + (size_t)f * CBP + (size_t)y * UP;
+                    for (int x = 0; x < U; ++x) if (row[x] != v0) { same = false; break; }
                 }
-            }
+            flat[k * RR + f] = same && !(c.debug_flags & XWB_DEBUG_EGO_NO_FLAT) ? (v0 == 255 ? 1 : 2) : 0;
         }
-        HIP_TRY(launch_xw_ego_build_tab(p, nullptr));
-        if (p.ego_cellinfo) HIP_TRY(launch_xw_ego_build_squares(p, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        if (p.ego_cellinfo) {
-            // which squares of the table are one flat colour (empty cells: 255; outside the map / shadow: 0): found by looking
-            // at the table itself, so the shortcut the gather takes for them (XwParams::ego_flat) cannot change a byte
-            const int r = c.visible_radius, U = ego_square(r).U, UP = ego_square(r).UP, RR = r * r, nc = p.ego_ncls;
-            const size_t CBP = (size_t)ego_square(r).plane, PBP = (size_t)RR * CBP, keys = (size_t)4 * nc * nc * nc;
-            std::vector<uint8_t> tab(xw_ego_square_tab_bytes(p)), flat(keys * RR, 0);
-            HIP_TRY(hipMemcpy(tab.data(), s->d_ego_tab3, tab.size(), hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < keys; ++k)
-                for (int f = 0; f < RR; ++f) {
-                    const uint8_t v0 = tab[k * p.channels * PBP + (size_t)f * CBP];
-                    bool same = v0 == 0 || v0 == 255;
-                    for (int chn = 0; chn < p.channels && same; ++chn)
-                        for (int y = 0; y < U && same; ++y) {
-                            const uint8_t *row = tab.data() + (k * p.channels + chn) * PBP + (size_t)f * CBP + (size_t)y * UP;
-                            for (int x = 0; x < U; ++x) if (row[x] != v0) { same = false; break; }
-                        }
-                    flat[k * RR + f] = same && !(c.debug_flags & XWB_DEBUG_EGO_NO_FLAT) ? (v0 == 255 ? 1 : 2) : 0;
-                }
-            if ((rc = dev_alloc(s, &s->d_ego_flat, flat.size()))) return rc;
-            HIP_TRY(hipMemcpy(s->d_ego_flat, flat.data(), flat.size(), hipMemcpyHostToDevice));
-            if ((rc = dev_alloc(s, &s->d_ego_constline, 256))) return rc;
-            HIP_TRY(hipMemset(s->d_ego_constline, 0xff, 128));
-            p.ego_flat = s->d_ego_flat; p.ego_constline = s->d_ego_constline;
-        }
-    }
+    XWB_TRY(dev_upload(s, &p.ego_flat, flat));
+    uint8_t *constline = nullptr;
+    XWB_TRY(dev_alloc(s, &constline, 256));
+    HIP_TRY(hipMemset(constline, 0xff, 128));
+    p.ego_constline = constline;
+    return XWB_OK;
+}
+
+// the egocentric view: goal poses and images, the 64-px atlas, the tap tables of the geometry, the table of whole frames, then
+// the goal-cell cache and the span path where they fit; the tables the device builds itself are built here
+int xw_ego_setup(xwb_sim *s) {
+    const xwb_config &c = s->cfg;
+    XwParams &p = s->xw;
+    const size_t n = (size_t)s->n;
+    XWB_TRY(dev_alloc(s, &p.goal_warp, n * XW_MAX_GOALS * 6));
+    XWB_TRY(dev_alloc(s, &p.goal_img, n * p.num_goals * 4096));
+    std::vector<uint8_t> a4;
+    std::vector<uint32_t> rot_off;
+    ego_atlas64(c, a4, rot_off);
+    XWB_TRY(dev_upload(s, &p.atlas64, a4));
+    XWB_TRY(dev_upload(s, &p.ego_agent_rot, rot_off));
+    EgoTap *taps = nullptr;
+    HIP_TRY(xw_ego_tables(c.visible_radius, c.max_dim, s->out_h, &taps, &p.ego_fast, &s->ego_cell_edge, &p.ego_span));
+    s->allocs.push_back(taps);
+    p.ego_taps = taps;
+    HIP_TRY(hipEventCreateWithFlags(&s->ev_view, hipEventDisableTiming | hipEventDisableSystemFence));
+    XWB_TRY(dev_alloc(s, &p.ego_tab, xw_ego_tab_bytes(p)));                     // filled by launch_xw_ego_build_tab
+    if (p.ego_fast && !(c.debug_flags & XWB_DEBUG_EGO_NO_CACHE)) XWB_TRY(ego_cache_alloc(s));
+    if (p.ego_cache) XWB_TRY(ego_span_alloc(s));
+    HIP_TRY(launch_xw_ego_build_tab(p, nullptr));
+    if (p.ego_cellinfo) HIP_TRY(launch_xw_ego_build_squares(p, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (p.ego_cellinfo) XWB_TRY(ego_flat_scan(s));
+    return XWB_OK;
+}
+
+int xw_setup(xwb_sim *s) {
+    NameTables names;
+    XWB_TRY(xw_check_config(s->cfg, names));
+    xw_fill_scalars(s, names);
+    xw_bind_shared(s);
+    XWB_TRY(xw_alloc_state(s));
+    XWB_TRY(xw_upload_palette(s, names));
+    XWB_TRY(xw_queue_objects(s));
+    if (s->cfg.visible_radius > 0) XWB_TRY(xw_ego_setup(s));
     return XWB_OK;
 }
 
@@ -597,8 +625,7 @@ int xwb_create(const xwb_config *cfg, xwb_sim **out) {
         std::vector<uint32_t> st((size_t)n);
         for (int e = 0; e < n; ++e)
             st[(size_t)e] = xwb_minstd_seed_thread(cfg->simulator_seed, cfg->thread_base + (int32_t)(cfg->env_gid0 + (uint32_t)e) + 1);
-        if ((rc = dev_alloc(s, &s->d_minstd, n))) return bail(rc);
-        HIP_TRY(hipMemcpy(s->d_minstd, st.data(), st.size() * 4, hipMemcpyHostToDevice));
+        if ((rc = dev_upload(s, &s->d_minstd, st))) return bail(rc);
     }
     if ((rc = dev_alloc(s, &s->d_actions, n, 0xff))) return bail(rc);
     if ((rc = dev_alloc(s, &s->d_actions_in, n, 0xff))) return bail(rc);
@@ -632,7 +659,7 @@ int xwb_create(const xwb_config *cfg, xwb_sim **out) {
     rc = xwb_reset(s, nullptr);
     if (rc) return bail(rc);
     HIP_TRY(hipDeviceSynchronize());
-    if (s->d_sync) {
+    if (s->xw.sync) {
         // the default stream is probed now (other streams: xwb_queue_sync_mode); the probe also re-selects the internal stream
         // when it shares the caller's hardware queue (side_beside, xwb_verbs.hip).  Forced modes and tools skip the probe in
         // use_epochs: the internal stream is still chosen, unless a tool serialises kernels (nothing would pass).
@@ -655,12 +682,8 @@ int xwb_destroy(xwb_sim *s) {
     if (s->d_sent_tab) (void)hipFree(s->d_sent_tab);
     if (s->h_poison) (void)hipHostFree(s->h_poison);
     if (s->side) (void)hipStreamDestroy(s->side);
-    if (s->ev_step) (void)hipEventDestroy(s->ev_step);
-    if (s->ev_reset) (void)hipEventDestroy(s->ev_reset);
-    if (s->ev_term) (void)hipEventDestroy(s->ev_term);
-    if (s->ev_cells) (void)hipEventDestroy(s->ev_cells);
-    if (s->ev_results) (void)hipEventDestroy(s->ev_results);
-    if (s->ev_view) (void)hipEventDestroy(s->ev_view);
+    for (hipEvent_t ev : {s->ev_step, s->ev_reset, s->ev_term, s->ev_cells, s->ev_results, s->ev_view})
+        if (ev) (void)hipEventDestroy(ev);
     for (KernelTimer *t : {&s->t_render, &s->t_step, &s->t_reset, &s->t_list})
         for (auto &ep : t->pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     delete s;

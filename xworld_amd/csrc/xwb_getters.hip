@@ -28,7 +28,7 @@ int redraw_env(xwb_sim *s, int32_t env) {
     const uint8_t two = 2;
     HIP_TRY(hipMemcpy(p.done_list, &env, 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(p.done_count, &cnt, 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_fresh + env, &two, 1, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->xw.fresh + env, &two, 1, hipMemcpyHostToDevice));
     if (p.visible_radius) HIP_TRY(launch_xw_warp_goals(p, true, nullptr));
     HIP_TRY(launch_xw_render(p, RENDER_LIST, nullptr));
     // (xwb_xw_pack_grids: one env redrawn out of turn -- a context ring elsewhere cannot follow that: context > 1 must
@@ -39,6 +39,23 @@ int redraw_env(xwb_sim *s, int32_t env) {
     s->list_valid = false;
     return XWB_OK;
 }
+
+// the icon a cell code shows (-1: an empty cell), and whether an icon is a goal of this batch's palette
+int icon_of(uint16_t code) { return (int)(code & XWB_CELL_ICON_MASK) - 1; }
+bool is_goal(const xwb_sim *s, int icon) { return icon >= 0 && icon < s->cfg.n_icons && s->icon_type_h[icon] == XWB_ICON_GOAL; }
+
+// The goal-slot table of a host grid (XwParams::goal_cells: the cell of goal slot i, 0xff = none): slots in row-major order, the
+// first XW_MAX_GOALS goals.  Returns how many goals the grid holds.
+int goal_slots(const xwb_sim *s, const uint16_t *grid, size_t cells, uint8_t gc[XW_MAX_GOALS]) {
+    memset(gc, 0xff, XW_MAX_GOALS);
+    int goals = 0;
+    for (size_t c = 0; c < cells; ++c)
+        if (is_goal(s, icon_of(grid[c])) && goals++ < XW_MAX_GOALS) gc[goals - 1] = (uint8_t)c;
+    return goals;
+}
+
+const char *const TASK_CLASS[9] = {"XWorld3DNavTarget", "XWorld3DNavTargetNear", "XWorld3DNavTargetBetween", "XWorld3DNavTargetDirection",
+                                   "XWorld3DNavTargetAvoid", "XWorldNavTarget", "XWorldNavNear", "XWorldNavColorTarget", "XWorldNavBetween"};
 
 }  // namespace
 
@@ -84,7 +101,7 @@ float xwb_minstd_rand_range(uint32_t *state, float upper) { return state ? xwb_m
 int xwb_xw_grid_dev(xwb_sim *s, uint16_t **ptr) {
     if (!s || !ptr) return fail(XWB_ERR_ARG, "NULL argument");
     if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_STATE, "not an xworld batch");
-    *ptr = s->d_grid;
+    *ptr = s->xw.grid;
     return XWB_OK;
 }
 
@@ -102,7 +119,7 @@ int xwb_done_count(xwb_sim *s, void *stream, int32_t *n_done) {
         *n_done = (int32_t)total;
         return XWB_OK;
     }
-    HIP_TRY(hipMemcpyAsync(n_done, s->d_done_count + s->count_sel, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(n_done, s->xw.done_count + s->count_sel, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return XWB_OK;
 }
@@ -160,12 +177,12 @@ int xwb_get_env_state(xwb_sim *s, int32_t env, void *stream, xwb_env_state *o) {
         HIP_TRY(hipMemcpyAsync(&o->race_y, s->d_y + env, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&o->race_angle, s->d_angle + env, 4, hipMemcpyDeviceToHost, st));
     } else {
-        HIP_TRY(hipMemcpyAsync(&axy, s->d_agent + env, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&ts, s->d_task_state + env, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&tsteps, s->d_task_steps + env, 4, hipMemcpyDeviceToHost, st));
-        if (s->d_task_state2) {
-            HIP_TRY(hipMemcpyAsync(&ts2, s->d_task_state2 + env, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(&tsteps2, s->d_task_steps2 + env, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&axy, s->xw.agent_xy + env, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&ts, s->xw.task_state + env, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&tsteps, s->xw.task_steps + env, 4, hipMemcpyDeviceToHost, st));
+        if (s->xw.task_state2) {
+            HIP_TRY(hipMemcpyAsync(&ts2, s->xw.task_state2 + env, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&tsteps2, s->xw.task_steps2 + env, 4, hipMemcpyDeviceToHost, st));
         }
     }
     HIP_TRY(hipStreamSynchronize(st));
@@ -183,27 +200,27 @@ int xwb_get_env_state(xwb_sim *s, int32_t env, void *stream, xwb_env_state *o) {
         o->xw_stage = (ts >> 16) & 0xf;
         o->xw_event = (ts >> 20) & 0xf;
         o->xw_steps_in_task = tsteps;
-        if (s->d_task_state2) {
+        if (s->xw.task_state2) {
             o->xw_task2 = (ts2 >> 24) & 0xf; o->xw_target2 = (int16_t)(ts2 & 0xffff); o->xw_stage2 = (ts2 >> 16) & 0xf;
             o->xw_event2 = (ts2 >> 20) & 0xf; o->xw_steps_in_task2 = tsteps2;
         }
         uint8_t dir = 1;
-        HIP_TRY(hipMemcpy(&dir, s->d_agent_dir + env, 1, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&dir, s->xw.agent_dir + env, 1, hipMemcpyDeviceToHost));
         o->xw_agent_dir = dir;
         o->xw_level = 0; o->xw_check_counter = 0;
-        if (s->d_cur_level) {
+        if (s->xw.cur_level) {
             uint8_t lv = 0;
-            HIP_TRY(hipMemcpy(&lv, s->d_cur_level + env, 1, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(&o->xw_check_counter, s->d_cur_counter + env, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&lv, s->xw.cur_level + env, 1, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&o->xw_check_counter, s->xw.cur_counter + env, 4, hipMemcpyDeviceToHost));
             o->xw_level = lv;
         }
         uint32_t sn = 0xffffffffu;
-        HIP_TRY(hipMemcpy(&sn, s->d_sent_names + env, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&sn, s->xw.sent_names + env, 4, hipMemcpyDeviceToHost));
         o->xw_sentence_names = sn;
         o->xw_group_first = o->xw_group_ran = -1;
-        if (s->d_grp_order) {
+        if (s->xw.grp_order) {
             uint8_t go = 0;
-            HIP_TRY(hipMemcpy(&go, s->d_grp_order + env, 1, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&go, s->xw.grp_order + env, 1, hipMemcpyDeviceToHost));
             o->xw_group_first = go & 1; o->xw_group_ran = (go >> 1) & 1;
         }
     }
@@ -254,7 +271,7 @@ int xwb_get_env_grid(xwb_sim *s, int32_t env, void *stream, uint16_t *out_host) 
     if (env < 0 || env >= s->n) return fail(XWB_ERR_ARG, "env out of range");
     hipStream_t st = as_stream(stream);
     const size_t cells = (size_t)s->cfg.max_dim * s->cfg.max_dim;
-    HIP_TRY(hipMemcpyAsync(out_host, s->d_grid + (size_t)env * cells, cells * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out_host, s->xw.grid + (size_t)env * cells, cells * 2, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return XWB_OK;
 }
@@ -267,37 +284,35 @@ int xwb_xw_load_map_task(xwb_sim *s, int32_t env, const uint16_t *grid_host, int
     if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_STATE, "not an xworld batch");
     if (s->cfg.n_tasks2 > 0) return fail(XWB_ERR_STATE, "map replay is for batches with one task group");
     if (env < 0 || env >= s->n) return fail(XWB_ERR_ARG, "env out of range");
-    if (s->d_cur_level) {
+    if (s->xw.cur_level) {
         if (dim < 3 || dim > 8) return fail(XWB_ERR_ARG, "dim is not one of the curriculum's levels (3..8)");
     } else if (dim != s->cfg.dim) return fail(XWB_ERR_ARG, "dim differs from the batch's dim");
     const int D = s->cfg.max_dim;
     if (agent_x < 0 || agent_y < 0 || agent_x >= D || agent_y >= D) return fail(XWB_ERR_ARG, "agent outside the map");
-    {   // the goal-slot table (XW_MAX_GOALS cells per env) is what the step kernel's "bumped into a goal" test reads
-        int goals = 0;
-        for (int c = 0; c < D * D; ++c) {
-            const int icon = (int)(grid_host[c] & XWB_CELL_ICON_MASK) - 1;
-            if (icon >= s->cfg.n_icons) return fail(XWB_ERR_ARG, "cell code beyond the palette");
-            if (icon >= 0 && s->icon_type_h[icon] == XWB_ICON_GOAL) goals++;
-        }
-        if (goals > XW_MAX_GOALS) return fail(XWB_ERR_ARG, "a map holds at most 16 goals");
-    }
+    const size_t cells = (size_t)D * D;
+    for (size_t c = 0; c < cells; ++c)
+        if (icon_of(grid_host[c]) >= s->cfg.n_icons) return fail(XWB_ERR_ARG, "cell code beyond the palette");
+    // the goal-slot table (XW_MAX_GOALS cells per env) is what the step kernel's "bumped into a goal" test reads; the egocentric
+    // render finds a goal's pose through it
+    uint8_t gc[XW_MAX_GOALS];
+    const int goals = goal_slots(s, grid_host, cells, gc);
+    if (goals > XW_MAX_GOALS) return fail(XWB_ERR_ARG, "a map holds at most 16 goals");
     HIP_TRY(hipDeviceSynchronize());
     pregen_invalidate(s);
-    const size_t cells = (size_t)D * D;
     int32_t axy = agent_x | (agent_y << 16);
     const bool is2d = task >= XWB_TASK2D_TARGET;
     if (is2d != (s->xw.group2d != 0)) return fail(XWB_ERR_ARG, "task is not of this batch's task family");
-    if (s->d_cur_level) {                                                // the level whose dims the map has
+    if (s->xw.cur_level) {                                                // the level whose dims the map has
         const uint8_t lv = (uint8_t)(dim - 3);
-        HIP_TRY(hipMemcpy(s->d_cur_level + env, &lv, 1, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->xw.cur_level + env, &lv, 1, hipMemcpyHostToDevice));
     }
     // stage NAV, no event (xw_device.h); a 2-D-native task without a target stays in its idle stage
     const int stage = is2d && target < 0 ? 0 : 1;
     int32_t ts = (target & 0xffff) | (stage << 16) | (task << 24);
     if (is2d) {
-        // the per-episode candidate tables of the step-time idle stages: goal slots in row-major order; reachable =
-        // same component as the agent with the blocks as the only obstacles (xworld_task.py:347-357)
-        std::vector<uint8_t> gc(XW_MAX_GOALS, 0xff), seen(cells, 0);
+        // the per-episode candidate table of the step-time idle stages: the goal slots that are reachable = in the same
+        // component as the agent with the blocks as the only obstacles (xworld_task.py:347-357)
+        std::vector<uint8_t> seen(cells, 0);
         std::vector<int> queue{agent_y * D + agent_x};
         seen[queue[0]] = 1;
         const int lo = (D - dim) / 2, hi = lo + dim;                     // XWorldEnv.set_dims offsets
@@ -307,45 +322,28 @@ int xwb_xw_load_map_task(xwb_sim *s, int32_t env, const uint16_t *grid_host, int
             for (auto &q : nb) {
                 if (q[0] < lo || q[1] < lo || q[0] >= hi || q[1] >= hi) continue;
                 const int nc = q[1] * D + q[0];
-                const int icon = (int)(grid_host[nc] & XWB_CELL_ICON_MASK) - 1;
-                if (icon >= s->cfg.n_icons) return fail(XWB_ERR_ARG, "cell code beyond the palette");
+                const int icon = icon_of(grid_host[nc]);
                 if (seen[nc] || (icon >= 0 && s->icon_type_h[icon] == XWB_ICON_BLOCK)) continue;
                 seen[nc] = 1;
                 queue.push_back(nc);
             }
         }
         uint32_t cand = 0;
-        int slot = 0;
-        for (size_t c = 0; c < cells && slot < XW_MAX_GOALS; ++c) {
-            const int icon = (int)(grid_host[c] & XWB_CELL_ICON_MASK) - 1;
-            if (icon < 0 || icon >= s->cfg.n_icons || s->icon_type_h[icon] != XWB_ICON_GOAL) continue;
-            gc[slot] = (uint8_t)c;
-            if (seen[c]) cand |= (1u << slot) | (s->icon_colored_h[icon] ? (1u << (16 + slot)) : 0u);
-            slot++;
-        }
-        HIP_TRY(hipMemcpy(s->d_goal_cells + (size_t)env * XW_MAX_GOALS, gc.data(), XW_MAX_GOALS, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->d_cand2d + env, &cand, 4, hipMemcpyHostToDevice));
-    } else {
-        // goal slot -> cell table (slots in row-major order): the egocentric render finds a goal's pose through it
-        std::vector<uint8_t> gc(XW_MAX_GOALS, 0xff);
-        int slot = 0;
-        for (size_t c = 0; c < cells && slot < XW_MAX_GOALS; ++c) {
-            const int icon = (int)(grid_host[c] & XWB_CELL_ICON_MASK) - 1;
-            if (icon >= 0 && icon < s->cfg.n_icons && s->icon_type_h[icon] == XWB_ICON_GOAL) gc[slot++] = (uint8_t)c;
-        }
-        HIP_TRY(hipMemcpy(s->d_goal_cells + (size_t)env * XW_MAX_GOALS, gc.data(), XW_MAX_GOALS, hipMemcpyHostToDevice));
-        if (s->d_goal_warp) {                               // default pose: yaw 1.5707963, scale 1, offset 0 = the identity warp
-            const double ident[6] = {1, 0, 0, 0, 1, 0};
-            for (int i = 0; i < XW_MAX_GOALS; ++i)
-                HIP_TRY(hipMemcpy(s->d_goal_warp + ((size_t)env * XW_MAX_GOALS + i) * 6, ident, sizeof ident, hipMemcpyHostToDevice));
-        }
+        for (int slot = 0; slot < goals; ++slot)
+            if (seen[gc[slot]]) cand |= (1u << slot) | (s->icon_colored_h[icon_of(grid_host[gc[slot]])] ? (1u << (16 + slot)) : 0u);
+        HIP_TRY(hipMemcpy(s->xw.cand2d + env, &cand, 4, hipMemcpyHostToDevice));
+    } else if (s->xw.goal_warp) {                           // default pose: yaw 1.5707963, scale 1, offset 0 = the identity warp
+        const double ident[6] = {1, 0, 0, 0, 1, 0};
+        for (int i = 0; i < XW_MAX_GOALS; ++i)
+            HIP_TRY(hipMemcpy(s->xw.goal_warp + ((size_t)env * XW_MAX_GOALS + i) * 6, ident, sizeof ident, hipMemcpyHostToDevice));
     }
+    HIP_TRY(hipMemcpy(s->xw.goal_cells + (size_t)env * XW_MAX_GOALS, gc, XW_MAX_GOALS, hipMemcpyHostToDevice));
     int32_t zero = 0;
     uint8_t z8 = 0;
-    HIP_TRY(hipMemcpy(s->d_grid + (size_t)env * cells, grid_host, cells * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_agent + env, &axy, 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_task_state + env, &ts, 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_task_steps + env, &zero, 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->xw.grid + (size_t)env * cells, grid_host, cells * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->xw.agent_xy + env, &axy, 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->xw.task_state + env, &ts, 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->xw.task_steps + env, &zero, 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->d_num_steps + env, &zero, 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s->d_done + env, &z8, 1, hipMemcpyHostToDevice));
     return redraw_env(s, env);                              // init_screen of that env
@@ -359,10 +357,10 @@ int xwb_xw_load_map(xwb_sim *s, int32_t env, const uint16_t *grid_host, int32_t 
     const size_t cells = (size_t)s->cfg.max_dim * s->cfg.max_dim;
     std::vector<uint16_t> g(grid_host, grid_host + cells);
     for (auto &c : g) {
-        const int icon = (int)(c & XWB_CELL_ICON_MASK) - 1;
+        const int icon = icon_of(c);
         c &= XWB_CELL_ICON_MASK;
         if (icon >= s->cfg.n_icons) return fail(XWB_ERR_ARG, "cell code beyond the palette");
-        if (icon >= 0 && s->icon_type_h[icon] == XWB_ICON_GOAL && s->icon_name_h[icon] == target_name) c |= XWB_CELL_TARGET;
+        if (is_goal(s, icon) && s->icon_name_h[icon] == target_name) c |= XWB_CELL_TARGET;
     }
     return xwb_xw_load_map_task(s, env, g.data(), agent_x, agent_y, dim, XWB_TASK_TARGET, target_name);
 }
@@ -374,7 +372,7 @@ int xwb_xw_set_agent_dir(xwb_sim *s, int32_t env, int32_t dir) {
     if (env < 0 || env >= s->n || dir < 0 || dir > 3) return fail(XWB_ERR_ARG, "env or dir out of range");
     HIP_TRY(hipDeviceSynchronize());
     const uint8_t d = (uint8_t)dir;
-    HIP_TRY(hipMemcpy(s->d_agent_dir + env, &d, 1, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->xw.agent_dir + env, &d, 1, hipMemcpyHostToDevice));
     return XWB_OK;
 }
 
@@ -386,14 +384,13 @@ int xwb_xw_set_goal_pose(xwb_sim *s, int32_t env, int32_t cell_x, int32_t cell_y
     if (env < 0 || env >= s->n || cell_x < 0 || cell_y < 0 || cell_x >= D || cell_y >= D) return fail(XWB_ERR_ARG, "env or cell out of range");
     HIP_TRY(hipDeviceSynchronize());
     uint8_t gc[XW_MAX_GOALS];
-    HIP_TRY(hipMemcpy(gc, s->d_goal_cells + (size_t)env * XW_MAX_GOALS, XW_MAX_GOALS, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(gc, s->xw.goal_cells + (size_t)env * XW_MAX_GOALS, XW_MAX_GOALS, hipMemcpyDeviceToHost));
     const int cell = cell_y * D + cell_x;
     int slot = xw_goal_slot_of(gc, cell);
     if (slot >= 0 && cell == 0xff) {                    // cell 255 of a 16 x 16 map reads like an empty slot: ask the grid
         uint16_t code = 0;
-        HIP_TRY(hipMemcpy(&code, s->d_grid + (size_t)env * D * D + cell, 2, hipMemcpyDeviceToHost));
-        const int icon = (int)(code & XWB_CELL_ICON_MASK) - 1;
-        if (xw_goal_slot_empty(gc, slot, icon >= 0 && icon < s->cfg.n_icons && s->icon_type_h[icon] == XWB_ICON_GOAL)) slot = -1;
+        HIP_TRY(hipMemcpy(&code, s->xw.grid + (size_t)env * D * D + cell, 2, hipMemcpyDeviceToHost));
+        if (xw_goal_slot_empty(gc, slot, is_goal(s, icon_of(code)))) slot = -1;
     }
     if (slot < 0) return fail(XWB_ERR_ARG, "no goal at that cell");
     // XItem::get_item_image (xitem.cpp:46-60) + the inversion cv::warpAffine performs
@@ -410,7 +407,7 @@ int xwb_xw_set_goal_pose(xwb_sim *s, int32_t env, int32_t cell_x, int32_t cell_y
     M[0] = A11; M[1] *= -Dt; M[3] *= -Dt; M[4] = A22;
     const double b1 = -M[0] * M[2] - M[1] * M[5], b2 = -M[3] * M[2] - M[4] * M[5];
     M[2] = b1; M[5] = b2;
-    HIP_TRY(hipMemcpy(s->d_goal_warp + ((size_t)env * XW_MAX_GOALS + slot) * 6, M, sizeof M, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->xw.goal_warp + ((size_t)env * XW_MAX_GOALS + slot) * 6, M, sizeof M, hipMemcpyHostToDevice));
     return XWB_OK;
 }
 
@@ -442,13 +439,11 @@ int xwb_get_extra_info(xwb_sim *s, int32_t env, void *stream, char *out, size_t 
     xwb_env_state st;
     int rc = xwb_get_env_state(s, env, stream, &st);
     if (rc) return rc;
-    static const char *tasks[] = {"XWorld3DNavTarget", "XWorld3DNavTargetNear", "XWorld3DNavTargetBetween", "XWorld3DNavTargetDirection",
-                                  "XWorld3DNavTargetAvoid", "XWorldNavTarget", "XWorldNavNear", "XWorldNavColorTarget", "XWorldNavBetween"};
     static const char *events[] = {"", "correct_goal", "wrong_goal", "time_up"};
-    const char *task = st.xw_task >= 0 && st.xw_task < 9 ? tasks[st.xw_task] : "";
+    const char *task = st.xw_task >= 0 && st.xw_task < 9 ? TASK_CLASS[st.xw_task] : "";
     const char *event = st.xw_event >= 0 && st.xw_event < 4 ? events[st.xw_event] : "";
     // xworld_.actual_height() / actual_width() (xworld.h:59,70): the level's dims under FLAGS_curriculum
-    const int dim = s->d_cur_level ? 3 + st.xw_level : s->cfg.dim;
+    const int dim = s->xw.cur_level ? 3 + st.xw_level : s->cfg.dim;
     snprintf(out, cap, "%d|task:%s,event:%s,height:%d,width:%d", (int)getpid(), task, event, dim, dim);
     return XWB_OK;
 }
@@ -462,7 +457,7 @@ static int env_sentence(xwb_sim *s, int32_t env, void *stream, std::string *out)
     auto packed = [](int task, int stage, int event, int target) { return task << 24 | event << 20 | stage << 16 | (target & 0xffff); };
     xwb::sent::EnvWords w;
     w.task_state = packed(st.xw_task, st.xw_stage, st.xw_event, st.xw_target); w.task_steps = st.xw_steps_in_task;
-    w.two = s->d_task_state2 != nullptr;
+    w.two = s->xw.task_state2 != nullptr;
     w.task_state2 = packed(st.xw_task2, st.xw_stage2, st.xw_event2, st.xw_target2); w.task_steps2 = st.xw_steps_in_task2;
     w.num_steps = (int32_t)st.num_steps;
     w.sent_names = st.xw_sentence_names;
@@ -473,7 +468,7 @@ static int env_sentence(xwb_sim *s, int32_t env, void *stream, std::string *out)
     auto cell = [&](int c) {                                  // one two-byte copy, and only when pick_env asks
         uint16_t code = 0;
         rc = [&]() -> int {
-            HIP_TRY(hipMemcpyAsync(&code, s->d_grid + (size_t)env * w.cells + c, 2, hipMemcpyDeviceToHost, as_stream(stream)));
+            HIP_TRY(hipMemcpyAsync(&code, s->xw.grid + (size_t)env * w.cells + c, 2, hipMemcpyDeviceToHost, as_stream(stream)));
             HIP_TRY(hipStreamSynchronize(as_stream(stream)));
             return XWB_OK;
         }();
@@ -606,9 +601,6 @@ int xwb_get_state_packet(xwb_sim *s, int32_t env, float reward, void *stream, ui
     return XWB_OK;
 }
 
-static const char *const TASK_CLASS[9] = {"XWorld3DNavTarget", "XWorld3DNavTargetNear", "XWorld3DNavTargetBetween", "XWorld3DNavTargetDirection",
-                                          "XWorld3DNavTargetAvoid", "XWorldNavTarget", "XWorldNavNear", "XWorldNavColorTarget", "XWorldNavBetween"};
-
 int xwb_get_task_performance(xwb_sim *s, void *stream, xwb_task_performance out[9], int64_t *resets) {
     if (!s || !out) return fail(XWB_ERR_ARG, "NULL argument");
     if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_STATE, "not a teaching environment");
@@ -616,7 +608,7 @@ int xwb_get_task_performance(xwb_sim *s, void *stream, xwb_task_performance out[
     XWB_LIVE(s);
     unsigned long long h[40];
     hipStream_t st = as_stream(stream);
-    HIP_TRY(hipMemcpyAsync(h, s->d_perf, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h, s->xw.perf, sizeof h, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int k = 0; k < 9; ++k) {
         out[k].successes = (int64_t)h[k * 4]; out[k].failures = (int64_t)h[k * 4 + 1];
@@ -650,9 +642,7 @@ int xwb_task_performance_report(xwb_sim *s, void *stream, char *out, size_t cap,
     static const int32_t only_target[1] = {XWB_TASK_TARGET};
     if (s->cfg.n_tasks > 0) add_group(s->cfg.tasks, s->cfg.n_tasks); else add_group(only_target, 1);
     add_group(s->cfg.tasks2, s->cfg.n_tasks2);
-    *need = text.size() + 1;
-    if (out && cap >= text.size() + 1) memcpy(out, text.c_str(), text.size() + 1);
-    return XWB_OK;
+    return copy_out(text, out, cap, need);
 }
 
 int xwb_decode_game_over_code(int32_t code, char *out, size_t cap) {

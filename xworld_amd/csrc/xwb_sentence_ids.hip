@@ -181,11 +181,12 @@ int xwb_sentence_ids(xwb_sim *s, int32_t *ids_dev, int32_t *len_dev, int32_t max
     p.silent_id = silent_id;
     p.seed = s->cfg.seed;
     p.gid0 = s->cfg.env_gid0;
-    p.task_state = s->d_task_state; p.task_steps = s->d_task_steps;
-    p.task_state2 = s->d_task_state2; p.task_steps2 = s->d_task_steps2;
-    p.num_steps = s->d_num_steps; p.episode = s->d_episode; p.sent_names = s->d_sent_names;
-    p.grp_order = s->d_grp_order;
-    p.grid = s->d_grid;
+    const XwParams &x = s->xw;
+    p.task_state = x.task_state; p.task_steps = x.task_steps;
+    p.task_state2 = x.task_state2; p.task_steps2 = x.task_steps2;
+    p.num_steps = s->d_num_steps; p.episode = s->d_episode; p.sent_names = x.sent_names;
+    p.grp_order = x.grp_order;
+    p.grid = x.grid;
     p.tab = s->sent_lay;
     p.ids = ids_dev; p.len = len_dev;
     const size_t tab_bytes = (size_t)p.tab.total * sizeof(int32_t);

@@ -2,6 +2,9 @@
 // translation units share (xwb_create.hip: configuration, set-up, create / destroy; xwb_verbs.hip: reset / step and the queue
 // hand-off; xwb_getters.hip: getters, per-env host access, packets, sentences; xwb_checkpoint.hip: save / load).
 //
+// Who owns a device buffer: the d_* members hold what all three games share, the simple games' own state and the few XWorld2D
+// buffers XwParams has no field for; every other XWorld2D buffer has ONE name, its field of xwb_sim::xw.
+//
 // A xwb_sim is the batched counterpart of simulator::SimulatorInterface (simulator_interface.h:40-89): it owns the SoA state
 // of num_envs environments in HBM and sequences the kernels in the reference's call order (simulator_interface.cpp:95-143).
 // No CPU fallback exists: without a usable gfx950 device xwb_create fails.
@@ -80,7 +83,8 @@ struct xwb_sim {
     int frame_src = 0, draws_since_pack = 0;
     bool draw_off = false;                 // xwb_xw_set_draw(sim, 0): frames are not drawn (their consumer draws them from xwb_xw_pack_grids)
     bool autoreset_done = false;           // the last step call already reset the envs whose codes are still set
-    // the done list lives in two buffers and its counter in three, rotated by every xworld step call (list_sel, count_sel): step k
+    // the done list lives in two buffers and its counter in three (xw.done_list, xw.done_ep, xw.done_count and xw.idle_count hold
+    // the bases, xw_params picks the current ones), rotated by every xworld step call (list_sel, count_sel): step k
     // appends to list k & 1 / counter k % 3 and zeroes counter (k + 1) % 3, so the regeneration pass of step k - 1, which reads that
     // step's list and counter on the internal queue, is never in the way -- only the one of step k - 2 has to be through
     int count_sel = 0, list_sel = 0;
@@ -90,7 +94,6 @@ struct xwb_sim {
     int last_path = XWB_PATH_NONE;         // xwb_step_path: which kernel sequence the last step call ran
     hipStream_t side = nullptr;            // reset of finished envs runs here, beside render_all
     uint32_t *d_minstd = nullptr;          // XWB_RNG_MINSTD: one engine state per env
-    uint32_t *d_sync = nullptr;            // device-side epochs of the step / reset kernels (XwParams::sync)
     uint32_t epoch_step = 0, epoch_reset = 0;
     // queue hand-off mode (include/xwb.h xwb_queue_sync_mode): decided per caller stream by a one-time probe
     struct StreamProbe { hipStream_t st; bool ok; int reason; };
@@ -118,12 +121,6 @@ struct xwb_sim {
     // simple_race
     float *d_x = nullptr, *d_y = nullptr, *d_angle = nullptr;
     xwb::RaceParams race{};
-    // xworld
-    uint16_t *d_grid = nullptr;
-    int32_t *d_task_steps2 = nullptr, *d_task_state2 = nullptr;
-    uint8_t *d_grp_order = nullptr;        // exclusive group scheduling (XwParams::grp_order)
-    int32_t *d_idle_list = nullptr, *d_idle_count = nullptr;
-    unsigned long long *d_perf = nullptr;  // XwParams::perf
     // pre-generated next episodes (XwParams::shadow / swap_shadow): xwb_step_autoreset's fast path
     bool pregen = false, shadow_ok = false, regen_pending = false, regen_by_epoch = false;
     bool regen_deferred = false;           // xwb_reset_done after a fused step: the pass is queued by the next verb (in the step's mode)
@@ -137,39 +134,7 @@ struct xwb_sim {
     int snap_sel = 0, snap_act_rep = 1;
     bool snap_ok = false;
     uint32_t snap_step = 0;
-    uint32_t *d_sh_ep = nullptr, *d_done_ep = nullptr;
-    uint8_t *d_sh_goal_cells = nullptr;
-    uint16_t *d_sh_grid = nullptr;
-    int32_t *d_sh_agent = nullptr, *d_sh_task_state = nullptr, *d_sh_task_state2 = nullptr;
-    uint32_t *d_sh_sent_names = nullptr, *d_sh_cand2d = nullptr;
-    int32_t *d_agent = nullptr, *d_task_steps = nullptr, *d_task_state = nullptr, *d_done_list = nullptr,
-            *d_done_count = nullptr;
-    uint8_t *d_fresh = nullptr, *d_icon_type = nullptr, *d_icon_colored = nullptr, *d_goal_cells = nullptr;
-    uint32_t *d_cand2d = nullptr, *d_sent_names = nullptr;
-    uint8_t *d_cur_level = nullptr, *d_cur_usage = nullptr;
-    int32_t *d_cur_counter = nullptr;
-    uint16_t *d_term_grid = nullptr;
-    uint8_t *d_term_flag = nullptr;
-    uint8_t *d_agent_dir = nullptr, *d_atlas64 = nullptr;
-    uint32_t *d_goal_img = nullptr, *d_agent_rot = nullptr;
-    xwb::EgoTap *d_ego_taps = nullptr;
-    uint8_t *d_ego_tab = nullptr;
     int ego_cell_edge = 1;
-    uint8_t *d_ego_cache = nullptr;        // lazily filled cache of rendered goal cells (XwParams::ego_cache)
-    uint32_t *d_ego_cache_valid = nullptr;
-    uint2 *d_ego_cellsrc = nullptr, *d_ego_cellsrc_list = nullptr;
-    uint2 *d_ego_miss_list = nullptr;
-    int32_t *d_ego_miss_count_list = nullptr;
-    uint32_t *d_ego_cellinfo = nullptr;    // span path of the egocentric render (XwParams::ego_span)
-    uint2 *d_ego_miss = nullptr;
-    int32_t *d_ego_miss_count = nullptr;
-    uint32_t *d_ego_xtab = nullptr;
-    uint2 *d_ego_clsimg = nullptr;
-    uint8_t *d_ego_cls = nullptr, *d_ego_tab3 = nullptr, *d_ego_flat = nullptr, *d_ego_constline = nullptr;
-    uint16_t *d_ego_cls_icon = nullptr;
-    double *d_goal_warp = nullptr;
-    int16_t *d_icon_name = nullptr, *d_name_first = nullptr, *d_name_variants = nullptr;
-    uint32_t *d_atlas = nullptr;
     uint8_t *d_view_atlas = nullptr;       // full observation, xwb_xw_render_view: [n_icons + 1][64][64][3] B,G,R (entry 0: a white cell)
     std::vector<uint8_t> tile_table;   // host copy, n_icons x c x 12 x 12
     std::vector<int32_t> icon_type_h, icon_name_h, icon_colored_h;
@@ -189,14 +154,14 @@ struct xwb_sim {
     int32_t *d_sent_tab = nullptr;
     size_t sent_tab_cap = 0;
     xwb::sent::SentTab sent_lay{};
-    xwb::XwParams xw{};
+    xwb::XwParams xw{};                // XWorld2D: scalars and buffers; verbs launch with xw_params(s), a copy with the per-call fields filled in
     std::vector<void *> allocs;
 };
 
 namespace xwb {
 namespace host {
 
-template <typename T>
+template <typename T>                      // (T may be const: the tables of XwParams the kernels only read)
 inline int dev_alloc(xwb_sim *s, T **p, size_t count, int fill = 0) {
     void *q = nullptr;
     size_t bytes = count * sizeof(T);
@@ -207,6 +172,20 @@ inline int dev_alloc(xwb_sim *s, T **p, size_t count, int fill = 0) {
     *p = static_cast<T *>(q);
     return XWB_OK;
 }
+
+// a table made on the host: allocates it (dev_alloc's rules; room for `room` elements where the device reads past the table's
+// end), uploads host[0 .. count) and assigns -- P is T, or const T for the read-only tables of XwParams, or the type the
+// kernels read the same bytes as
+template <typename P, typename T>
+inline int dev_upload(xwb_sim *s, P **p, const T *host, size_t count, size_t room = 0) {
+    T *q = nullptr;
+    if (const int rc = dev_alloc(s, &q, count > room ? count : room)) return rc;
+    if (count) HIP_TRY(hipMemcpy(q, host, count * sizeof(T), hipMemcpyHostToDevice));
+    *p = reinterpret_cast<P *>(q);
+    return XWB_OK;
+}
+template <typename P, typename T>
+inline int dev_upload(xwb_sim *s, P **p, const std::vector<T> &host, size_t room = 0) { return dev_upload(s, p, host.data(), host.size(), room); }
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

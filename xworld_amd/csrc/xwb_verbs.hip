@@ -45,20 +45,20 @@ uint32_t next_epoch(uint32_t &e) {
 bool epoch_probe(xwb_sim *s, hipStream_t st, int *reason) {
     auto bad = [&](int why) { (void)hipGetLastError(); *reason = why; return false; };
     if (hipStreamSynchronize(st) != hipSuccess || hipStreamSynchronize(s->side) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
-    if (hipMemsetAsync(s->d_sync + SYNC_PROBE_EXPIRED, 0, sizeof(uint32_t), s->side) != hipSuccess || hipStreamSynchronize(s->side) != hipSuccess)
+    if (hipMemsetAsync(s->xw.sync + SYNC_PROBE_EXPIRED, 0, sizeof(uint32_t), s->side) != hipSuccess || hipStreamSynchronize(s->side) != hipSuccess)
         return bad(XWB_SYNC_REASON_PROBE_ERROR);
     for (int dir = 0; dir < 2; ++dir) {
         hipStream_t waiter = dir ? st : s->side, publisher = dir ? s->side : st;
         next_epoch(s->probe_token);
-        if (launch_xw_wait(s->d_sync + SYNC_PROBE, s->probe_token, s->d_sync + SYNC_PROBE_EXPIRED, nullptr, waiter, 200000ull) != hipSuccess)   // 2 ms
+        if (launch_xw_wait(s->xw.sync + SYNC_PROBE, s->probe_token, s->xw.sync + SYNC_PROBE_EXPIRED, nullptr, waiter, 200000ull) != hipSuccess)   // 2 ms
             return bad(XWB_SYNC_REASON_PROBE_ERROR);
-        if (launch_xw_signal(s->d_sync + SYNC_PROBE, s->probe_token, publisher) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
+        if (launch_xw_signal(s->xw.sync + SYNC_PROBE, s->probe_token, publisher) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
         if (hipStreamSynchronize(waiter) != hipSuccess || hipStreamSynchronize(publisher) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
     }
     uint32_t expired = 1;
-    if (hipMemcpy(&expired, s->d_sync + SYNC_PROBE_EXPIRED, sizeof expired, hipMemcpyDeviceToHost) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
+    if (hipMemcpy(&expired, s->xw.sync + SYNC_PROBE_EXPIRED, sizeof expired, hipMemcpyDeviceToHost) != hipSuccess) return bad(XWB_SYNC_REASON_PROBE_ERROR);
     if (expired) {
-        (void)hipMemset(s->d_sync + SYNC_PROBE_EXPIRED, 0, sizeof(uint32_t));
+        (void)hipMemset(s->xw.sync + SYNC_PROBE_EXPIRED, 0, sizeof(uint32_t));
         *reason = XWB_SYNC_REASON_PROBE_FAILED;
         return false;
     }
@@ -113,7 +113,7 @@ bool side_beside(xwb_sim *s, hipStream_t st, int *reason) {
 // may_probe: only xwb_create (the default stream) and xwb_queue_sync_mode (any stream, an explicit call) run the probe -- it
 // synchronises both streams and the host; the step verbs never do: a stream nobody probed hands over through events.
 bool use_epochs(xwb_sim *s, hipStream_t st, bool may_probe) {
-    if (!s->d_sync || !s->side) { s->sync_reason = XWB_SYNC_REASON_NOT_USED; return false; }
+    if (!s->xw.sync || !s->side) { s->sync_reason = XWB_SYNC_REASON_NOT_USED; return false; }
     if (s->cfg.queue_sync == XWB_QUEUE_SYNC_EVENTS) { s->sync_reason = XWB_SYNC_REASON_CONFIG; return false; }
     if (s->cfg.queue_sync == XWB_QUEUE_SYNC_EPOCHS) { s->sync_reason = XWB_SYNC_REASON_CONFIG; return true; }
     int why = 0;
@@ -211,6 +211,8 @@ int simple_launch(xwb_sim *s, int mode, const uint8_t *mask, const int32_t *acti
     return XWB_OK;
 }
 
+// The parameters of a launch: s->xw with the fields that change from call to call -- the caller's frames and results slot, the
+// policy's step number, and the current buffers of the rotations, whose bases s->xw holds (xwb_sim.h count_sel, list_sel)
 XwParams xw_params(xwb_sim *s) {
     XwParams p = s->xw;
     p.obs = static_cast<uint8_t *>(s->d_obs);
@@ -218,11 +220,11 @@ XwParams xw_params(xwb_sim *s) {
     p.policy_step = s->policy_step;
     p.no_draw = s->draw_off ? 1 : 0;
     p.list_flag = 2;
-    p.done_list = s->d_done_list + (size_t)s->list_sel * (size_t)s->n;
-    p.done_ep = s->d_done_ep + (size_t)s->list_sel * (size_t)s->n;
-    p.done_count = s->d_done_count + s->count_sel;
-    p.done_count_next = s->d_done_count + (s->count_sel + 1) % 3;
-    if (s->d_idle_count) { p.idle_count = s->d_idle_count + s->count_sel; p.idle_count_next = s->d_idle_count + (s->count_sel + 1) % 3; }
+    p.done_list += (size_t)s->list_sel * (size_t)s->n;
+    p.done_ep += (size_t)s->list_sel * (size_t)s->n;
+    p.done_count_next = p.done_count + (s->count_sel + 1) % 3;
+    p.done_count += s->count_sel;
+    if (p.idle_count) { p.idle_count_next = p.idle_count + (s->count_sel + 1) % 3; p.idle_count += s->count_sel; }
     return p;
 }
 
@@ -230,8 +232,8 @@ XwParams xw_params(xwb_sim *s) {
 XwParams shadow_params(xwb_sim *s) {
     XwParams q = xw_params(s);
     q.shadow = 1; q.auto_reset = AUTO_RESET_KEEP; q.sig_epoch = 0; q.wait_epoch = 0; q.packed = nullptr;
-    q.grid = s->d_sh_grid; q.agent_xy = s->d_sh_agent; q.task_state = s->d_sh_task_state; q.task_state2 = s->d_sh_task_state2;
-    q.sent_names = s->d_sh_sent_names; q.cand2d = s->d_sh_cand2d; q.goal_cells = s->d_sh_goal_cells;
+    q.grid = q.sh_grid; q.agent_xy = q.sh_agent_xy; q.task_state = q.sh_task_state; q.task_state2 = q.sh_task_state2;
+    q.sent_names = q.sh_sent_names; q.cand2d = q.sh_cand2d; q.goal_cells = q.sh_goal_cells;
     return q;
 }
 
@@ -246,14 +248,14 @@ const HandOver TERM_DONE{SYNC_SPAN_TERM, &xwb_sim::ev_term};
 
 // publish `h` on queue `q`: behind the work queued there so far (a one-thread signal kernel, or an event record)
 int publish(xwb_sim *s, const HandOver &h, bool by_epoch, uint32_t epoch, hipStream_t q) {
-    if (by_epoch) HIP_TRY(launch_xw_signal(s->d_sync + h.slot, epoch, q));
+    if (by_epoch) HIP_TRY(launch_xw_signal(s->xw.sync + h.slot, epoch, q));
     else HIP_TRY(hipEventRecord(s->*h.ev, q));
     return XWB_OK;
 }
 
 // order the work queued on `q` from here on after `h` (a one-wavefront waiter under the batch's watchdog, or an event wait)
 int order_after(xwb_sim *s, const HandOver &h, bool by_epoch, uint32_t epoch, hipStream_t q) {
-    if (by_epoch) HIP_TRY(launch_xw_wait(s->d_sync + h.slot, epoch, s->d_sync + SYNC_POISON, s->xw.poison_host, q));
+    if (by_epoch) HIP_TRY(launch_xw_wait(s->xw.sync + h.slot, epoch, s->xw.sync + SYNC_POISON, s->xw.poison_host, q));
     else HIP_TRY(hipStreamWaitEvent(q, s->*h.ev, 0));
     return XWB_OK;
 }
@@ -758,7 +760,7 @@ int xwb_check_errors(xwb_sim *s, void *stream, int32_t *n_bad) {
     HIP_TRY(hipMemcpyAsync(n_bad, s->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemsetAsync(s->d_err, 0, sizeof(int32_t), st));
     uint32_t timed_out = 0;
-    if (s->d_sync) HIP_TRY(hipMemcpyAsync(&timed_out, s->d_sync + SYNC_POISON, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (s->xw.sync) HIP_TRY(hipMemcpyAsync(&timed_out, s->xw.sync + SYNC_POISON, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (timed_out) s->poisoned = true;                 // sticky: the device word is never cleared
     XWB_LIVE(s);
@@ -793,11 +795,11 @@ int xwb_queue_sync_forget(xwb_sim *s, void *stream) {
 
 int xwb_debug_stall_handoff(xwb_sim *s, void *stream, int64_t budget_us) {
     if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
-    if (!s->d_sync) return fail(XWB_ERR_STATE, "this game has no queue hand-off");
+    if (!s->xw.sync) return fail(XWB_ERR_STATE, "this game has no queue hand-off");
     if (budget_us < 1 || budget_us > 10000000) return fail(XWB_ERR_ARG, "budget_us must be in 1..10 000 000");
     XWB_ON_DEVICE(s);
     // (the probe's slot: its tokens count up from 1, so this value is never reached)
-    HIP_TRY(launch_xw_wait(s->d_sync + SYNC_PROBE, 0x7fffffffu, s->d_sync + SYNC_POISON, s->xw.poison_host, as_stream(stream), (unsigned long long)budget_us * 100ull));
+    HIP_TRY(launch_xw_wait(s->xw.sync + SYNC_PROBE, 0x7fffffffu, s->xw.sync + SYNC_POISON, s->xw.poison_host, as_stream(stream), (unsigned long long)budget_us * 100ull));
     return XWB_OK;
 }
 
