@@ -258,7 +258,8 @@ int xwb_step_n(xwb_sim *sim, int32_t n_steps, int32_t act_rep, void *stream);
 enum { XWB_RUN_AUTORESET = 1 };
 int xwb_run(xwb_sim *sim, int32_t iterations, int32_t act_rep, int32_t flags, void *stream);
 
-/* returns the number of envs that flagged an out-of-range action since the last call (synchronises stream).
+/* returns the number of envs that flagged an out-of-range action since the last call, plus the pairs xwb_copy_envs skipped for an
+ * index outside a batch with this batch as the destination (synchronises stream).
  * Fails with XWB_ERR_STATE when the batch is poisoned (see xwb_queue_sync_mode). */
 int xwb_check_errors(xwb_sim *sim, void *stream, int32_t *n_bad);
 
@@ -625,6 +626,53 @@ enum { XWB_SYM_EMPTY = 0, XWB_SYM_GOAL = 1, XWB_SYM_BLOCK = 2, XWB_SYM_AGENT = 3
 enum { XWB_SYM_PLANE_KIND = 0, XWB_SYM_PLANE_ICON = 1, XWB_SYM_PLANE_NAME = 2, XWB_SYM_PLANES = 3 };
 int xwb_xw_symbolic_dims(const xwb_sim *sim, size_t *planes, size_t *rows, size_t *cols);
 int xwb_xw_symbolic(xwb_sim *sim, int16_t *out_dev, size_t out_bytes, void *stream);
+
+/* ---- fork envs on the device: put an env into a chosen state ----
+ * xwb_copy_envs: for i in [0, n), env dst_envs_dev[i] of `dst` becomes a copy of env src_envs_dev[i] of `src` -- the primitive
+ * behind look-ahead and tree search on the true dynamics (fork, try each action, keep the best), "return to a stored state",
+ * and restarting many slots from a few prepared levels (build K levels once in a small template batch with
+ * xwb_xw_load_map_task, scatter them into a working batch of any size).  ALE calls it cloneState / restoreState; the reference
+ * has no such call.  Both lists are int32 in DEVICE memory (4-byte aligned).  dst == src is allowed (the fork within a batch);
+ * repeats in the source list are allowed; a pair with dst == src and the same index is a no-op.  An env that appears twice in
+ * the destination list, or in both lists of one batch, ends up with UNSPECIFIED contents (its bytes come from either writer, or
+ * from a source read while it was being written); every access stays inside the batches' arrays.  n == 0 does nothing.
+ * What a copy is: every per-env array xwb_save_state writes -- actions, num_steps, episode, reward, game_over code, success;
+ * SimpleGame pos / flags; SimpleRace x / y / angle; the XWB_RNG_MINSTD engine; XWorld2D grid, agent cell and heading, both
+ * groups' task state and task steps, the exclusive schedule's group order, the goal-slot table, reachable-goal sets, bound
+ * sentence names, goal poses, the context ring's flag and the three curriculum arrays -- plus the env's bytes_per_env bytes of
+ * the observation buffer currently bound (xwb_bind_obs; context ring and float32 frames included).  Egocentric batches: the
+ * destination's warped goal images are copied with the poses, and what the render cached of its goal cells is dropped.  NOT
+ * copied, because they are not per-env state: the error counter, the per-workgroup reset counts, the done list and its
+ * counters, the task performance counters, the caller's bound result tensors.  Nothing changes in `src` when src != dst.
+ * XWB_COPY_KEEP_RNG: the destination keeps its own episode counter and XWB_RNG_MINSTD engine -- its future resets stay its own;
+ * the mode for scattering template levels.
+ * What a copy is NOT: the counter-based RNG is keyed by the slot's global env id, so a clone's next reset, the wording of its
+ * sentence (stream 3: xwb_sentence of a clone is the slot's own wording of the source's bound names) and any step-time
+ * idle-stage draw (the 2-D-native group, exclusive scheduling) are the destination slot's own; the bound names, target, stage
+ * and time limits are the source's.  For a batch with one XWorld3DNav* group a clone driven by the same explicit actions
+ * follows its source exactly until the episode ends; the simple games under XWB_RNG_MINSTD follow it for ever after an exact
+ * (not KEEP_RNG) fork.
+ * When: wherever every env of both batches is live -- after xwb_reset, xwb_reset_done, xwb_reset_masked, xwb_reset_env,
+ * xwb_step_autoreset, xwb_step_n, xwb_run, xwb_load_state, the map replay hooks.  Between xwb_step (or xwb_step_host) and its
+ * xwb_reset_done the terminal snapshots and the done list describe envs the copy would overwrite: XWB_ERR_STATE, decided from
+ * the host's record of the last verb, no device read.  (A finished env cannot be copied before its reset.)
+ * XWB_ERR_ARG, nothing launched: NULL batches or lists, n < 0, unknown flag bits, batches on different devices, batches that do
+ * not share everything that shapes an env's state -- the game, bytes_per_env and every configuration field except num_envs,
+ * seed, policy_seed, env_gid0, simulator_seed, thread_base (and queue_sync, debug_flags).  A poisoned batch: XWB_ERR_STATE.
+ * An index outside [0, num_envs) of its batch cannot be seen by the host: the kernel skips that pair whole and adds one to the
+ * DESTINATION's error counter -- xwb_check_errors counts such pairs together with the out-of-range actions.
+ * Cost and order: ONE kernel launch on `stream` (workgroups over pairs x 4 KB pieces of the env, so a short list still fills the
+ * device); no allocation, no host synchronisation.  The caller orders the earlier verbs of BOTH batches onto `stream`.  For the
+ * destination the call does what xwb_reset_masked does: it waits for a pending regeneration pass, the pre-generated episodes
+ * become stale (xwb_step_path's shadow_breaks counts it where they were live; a loop that forks every step ends on the classic
+ * path after three breaks, like a loop of masked resets -- also with XWB_COPY_KEEP_RNG: keeping them valid is not attempted),
+ * and the next xwb_step runs as two launches once.  Egocentric batches: one event orders the internal queue's later work behind
+ * the kernel, as for xwb_xw_render_view.  xwb_xw_pack_grids afterwards: context 1 reports the copied envs' cell codes like any
+ * other env's; with context > 1 a copy replaces whole rings, which a holder elsewhere cannot replay -- the pack is refused
+ * (XWB_ERR_STATE) as after a map replay: re-synchronise with the screens. */
+enum { XWB_COPY_KEEP_RNG = 1 };
+int xwb_copy_envs(xwb_sim *dst, const int32_t *dst_envs_dev, xwb_sim *src, const int32_t *src_envs_dev, int32_t n, int32_t flags,
+                  void *stream);
 
 /* (test and measurement hooks -- xwb_debug_stall_handoff, xwb_profile_begin / _end / _stop -- are not part of this boundary:
  * include/xwb_testing.h, version node XWB_TESTING of csrc/libxwb.map) */

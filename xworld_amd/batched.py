@@ -537,6 +537,46 @@ class BatchedSimulator:
         lib.check(self.L.xwb_xw_symbolic(self.h, C.c_void_p(out.data_ptr()), out.numel() * 2, self._stream(stream)))
         return out
 
+    def _env_list(self, name, envs, dev):
+        """an index list of copy_envs as a contiguous 1-d int32 tensor on `dev`: an int32 CUDA tensor is used as it is (no host
+        round trip), anything else torch.as_tensor takes is converted on the host (the caller moves it once the lists are checked)"""
+        import torch
+        if isinstance(envs, torch.Tensor) and envs.is_cuda:
+            if envs.dtype != torch.int32 or envs.dim() != 1 or not envs.is_contiguous() or envs.device != dev:
+                raise ValueError("%s: a contiguous 1-d int32 tensor on %s" % (name, dev))
+            return envs
+        host = torch.as_tensor(envs)
+        if host.dim() > 1 or (host.numel() and (host.dtype.is_floating_point or host.dtype.is_complex or host.dtype == torch.bool)):
+            raise ValueError("%s: a 1-d sequence of integer env indices" % name)
+        return host.reshape(-1).to(torch.int32)
+
+    def copy_envs(self, dst_envs, src_envs, source=None, keep_rng=False, stream=None):
+        """xwb_copy_envs: env dst_envs[i] of this batch becomes a copy of env src_envs[i] of `source` (default: this batch -- the
+        fork inside a batch) -- state, task, frames, everything save_state holds per env -- in one kernel launch on `stream`, no
+        host round trip.  The lists: int32 CUDA tensors (used as they are) or anything torch.as_tensor takes; equal lengths
+        (ValueError otherwise).  Repeats among the sources are fine; an env listed twice as a destination, or as a destination and a
+        source of one batch, ends up unspecified.  An index outside a batch skips its pair and shows up in check_errors().
+        keep_rng: the destination keeps its own episode counter (and minstd engine): its later resets stay its own -- the mode for
+        scattering a few template levels over a batch.  `source` must share this batch's configuration apart from num_envs, the
+        seeds and env_gid0.  Not between step() and its reset_done() (XwbError).  Returns self."""
+        import torch
+        src = self if source is None else source
+        if not isinstance(src, BatchedSimulator):
+            raise ValueError("source: a BatchedSimulator (or None for this batch)")
+        dev = torch.device("cuda", self.device)
+        d = self._env_list("dst_envs", dst_envs, dev)
+        s = self._env_list("src_envs", src_envs, dev)
+        if d.numel() != s.numel():
+            raise ValueError("copy_envs: %d destination envs for %d source envs" % (d.numel(), s.numel()))
+        n = int(d.numel())
+        d, s = d.to(dev), s.to(dev)
+        if n == 0:                                             # (an empty tensor has no address: the library still checks the rest)
+            d = s = torch.zeros(1, dtype=torch.int32, device=dev)
+        lib.check(self.L.xwb_copy_envs(self.h, C.c_void_p(d.data_ptr()), src.h, C.c_void_p(s.data_ptr()), n,
+                                       lib.XWB_COPY_KEEP_RNG if keep_rng else 0, self._stream(stream)))
+        self._copy_lists = (d, s)                              # (keeps lists copied from the host alive until the next call)
+        return self
+
     def env_state(self, env=0, stream=None):
         st = lib.XwbEnvState()
         lib.check(self.L.xwb_get_env_state(self.h, int(env), self._stream(stream), C.byref(st)))

@@ -434,6 +434,30 @@ size_t xw_ego_square_entry_bytes(const XwParams &p);
 size_t xw_ego_xtab_bytes(const XwParams &p);
 hipError_t launch_xw_ego_build_squares(const XwParams &p, hipStream_t s);
 
+// ------------------------------------------------------------- copy envs ---
+// xwb_copy_envs (kernels_copy_envs.hip): for every pair i, env dst_envs[i] of the destination arrays becomes env src_envs[i] of
+// the source arrays.  The arrays travel by value: `small` holds those of at most COPY_SMALL bytes per env (one workgroup per
+// pair copies them all, eight lanes each), `big` the rest, cut into chunks of COPY_CHUNK bytes (one workgroup per pair and chunk).
+constexpr int COPY_BS = 256;                 // threads of a workgroup
+constexpr int COPY_CHUNK = COPY_BS * 16;     // bytes of one chunk: 16 per lane
+constexpr int COPY_SMALL = 64;               // largest per-env size of a "small" array
+constexpr int COPY_MAX_SMALL = 32, COPY_MAX_BIG = 12;
+struct CopyArray {
+    const uint8_t *src;          // base of the source batch's array; null: the destination env's bytes are zeroed
+    uint8_t *dst;
+    uint32_t bytes;              // per env
+    uint32_t chunk0;             // big arrays: the pair's first chunk that belongs to this one (chunk 0 is the small arrays')
+};
+struct CopyEnvsParams {
+    CopyArray small[COPY_MAX_SMALL], big[COPY_MAX_BIG];
+    int n_small, n_big, chunks;  // chunks: per pair, the small arrays' included
+    int n_pairs, n_src, n_dst;   // n_src, n_dst: num_envs of the two batches
+    int same;                    // one batch: a pair with dst == src is a no-op
+    const int32_t *src_envs, *dst_envs;
+    int32_t *err_count;          // the destination's: pairs skipped for an index outside its batch
+};
+hipError_t launch_copy_envs(const CopyEnvsParams &p, hipStream_t s);
+
 // host: builds the 12x12 tile table (OpenCV 3.2 fixed-point bilinear + BGR2GRAY) from 64x64 icons
 void build_tile_table(const uint8_t *icons64, int n_icons, int channels, uint8_t *out /* n*c*12*12 */);
 

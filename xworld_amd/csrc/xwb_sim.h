@@ -1,6 +1,6 @@
 // xwb_sim.h -- internal to libxwb.so: the batch object behind the opaque xwb_sim of include/xwb.h, and what the host-side
 // translation units share (xwb_create.hip: configuration, set-up, create / destroy; xwb_verbs.hip: reset / step and the queue
-// hand-off; xwb_getters.hip: getters, per-env host access, packets, sentences; xwb_checkpoint.hip: save / load).
+// hand-off; xwb_getters.hip: getters, per-env host access, packets, sentences; xwb_checkpoint.hip: save / load / copy envs).
 //
 // Who owns a device buffer: the d_* members hold what all three games share, the simple games' own state and the few XWorld2D
 // buffers XwParams has no field for; every other XWorld2D buffer has ONE name, its field of xwb_sim::xw.
@@ -83,6 +83,7 @@ struct xwb_sim {
     int frame_src = 0, draws_since_pack = 0;
     bool draw_off = false;                 // xwb_xw_set_draw(sim, 0): frames are not drawn (their consumer draws them from xwb_xw_pack_grids)
     bool autoreset_done = false;           // the last step call already reset the envs whose codes are still set
+    bool step_open = false;                // a plain step call's finished envs still await their reset: xwb_copy_envs is refused
     // the done list lives in two buffers and its counter in three (xw.done_list, xw.done_ep, xw.done_count and xw.idle_count hold
     // the bases, xw_params picks the current ones), rotated by every xworld step call (list_sel, count_sel): step k
     // appends to list k & 1 / counter k % 3 and zeroes counter (k + 1) % 3, so the regeneration pass of step k - 1, which reads that

@@ -490,6 +490,7 @@ int do_step(xwb_sim *s, const int32_t *actions_dev, int32_t act_rep, bool autore
     s->policy_step += 1;
     s->packed_pos += 1;
     s->autoreset_done = autoreset;
+    s->step_open = !autoreset;
     return XWB_OK;
 }
 
@@ -644,6 +645,7 @@ int xwb_reset(xwb_sim *s, void *stream) {
     XWB_LIVE(s);
     hipStream_t st = as_stream(stream);
     s->autoreset_done = false;
+    s->step_open = false;
     if (s->cfg.game != XWB_XWORLD2D) return simple_launch(s, MODE_RESET_ALL, nullptr, nullptr, 1, false, 1, st);
     return run_reset(s, MODE_RESET_ALL, st);
 }
@@ -653,6 +655,7 @@ int xwb_reset_done(xwb_sim *s, void *stream) {
     XWB_ON_DEVICE(s);
     XWB_LIVE(s);
     hipStream_t st = as_stream(stream);
+    s->step_open = false;
     if (s->autoreset_done) {
         // xwb_step_autoreset / xwb_step_n already reset every env whose code is set (the codes are kept for the caller
         // to read): clearing them is all that is left -- resetting those envs again would skip an episode
@@ -671,6 +674,7 @@ int xwb_reset_masked(xwb_sim *s, const uint8_t *mask_dev, void *stream) {
     XWB_ON_DEVICE(s);
     XWB_LIVE(s);
     hipStream_t st = as_stream(stream);
+    s->step_open = false;                  // (which envs a mask restarts is the caller's business)
     if (s->cfg.game != XWB_XWORLD2D) return simple_launch(s, MODE_RESET_MASK, mask_dev, nullptr, 1, false, 1, st);
     XWB_TRY(rebuild_done_list(s, MODE_RESET_MASK, mask_dev, st));
     return run_reset(s, MODE_RESET_MASK, st);
@@ -731,6 +735,7 @@ int xwb_step_n(xwb_sim *s, int32_t n_steps, int32_t act_rep, void *stream) {
     s->policy_step += (uint32_t)n_steps;
     s->packed_pos += 1;
     s->autoreset_done = true;
+    s->step_open = false;
     return XWB_OK;
 }
 

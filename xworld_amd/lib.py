@@ -18,6 +18,7 @@ XWB_MAP_NAV, XWB_MAP_WALLS = 0, 1
 XWB_TASKMODE_LANG_ACQ, XWB_TASKMODE_ONE_CHANNEL = 0, 1
 ALIVE, MAX_STEP, DEAD, SUCCESS, LOST_LIFE = 0, 1, 2, 4, 8
 XWB_QUEUE_SYNC_AUTO, XWB_QUEUE_SYNC_EVENTS, XWB_QUEUE_SYNC_EPOCHS = 0, 1, 2
+XWB_COPY_KEEP_RNG = 1
 DEBUG_FLAGS = {"no_pregen": 1, "no_lazy": 2, "ego_no_cache": 4, "ego_no_span": 8, "ego_no_flat": 16, "no_fused": 32}
 STEP_PATHS = ["none", "classic", "lazy", "pregen", "ego_span", "ego_per_env", "lazy_fused"]
 SYNC_REASONS = ["probe_ok", "config", "env", "tool", "probe_failed", "probe_error", "not_used", "not_probed"]
@@ -169,6 +170,7 @@ _SIGS = [
     ("xwb_xw_expert", C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),
     ("xwb_xw_symbolic_dims", C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("xwb_xw_symbolic", C.c_int, [_vp, _vp, C.c_size_t, _vp]),
+    ("xwb_copy_envs", C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     ("xwb_run", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     ("xwb_last_error", C.c_char_p, []),
     ("xwb_version", C.c_char_p, []),
