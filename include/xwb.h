@@ -674,6 +674,51 @@ enum { XWB_COPY_KEEP_RNG = 1 };
 int xwb_copy_envs(xwb_sim *dst, const int32_t *dst_envs_dev, xwb_sim *src, const int32_t *src_envs_dev, int32_t n, int32_t flags,
                   void *stream);
 
+/* ---- evaluate action plans on the true dynamics: what a sequence of actions would pay ----
+ * xwb_xw_evaluate_plans answers, for chosen envs of an XWorld2D batch and n_plans action sequences of length horizon per env,
+ * what xwb_step would pay for each of them -- without stepping, forking or writing anything: the read-only counterpart of
+ * "xwb_copy_envs into child slots, step, reset_done" for random shooting, CEM, MPC, n-step look-ahead and the rollout values of
+ * a tree search (leaf value: xwb_xw_expert's field at `last`).  Under one XWorld3DNav* task group a step draws no random number
+ * and moves nothing but the agent, so a plan's outcome is a function of the env's current state and the plan's action ids.
+ *   envs_dev    NULL: every env, row i = env i (n is ignored and taken as num_envs); else n env indices in DEVICE memory (int32,
+ *               repeats allowed).  An index outside [0, num_envs) cannot be seen by the host: each of its plans reports steps -1,
+ *               return 0, code 0, last -1, and the batch's error counter goes up by one (xwb_check_errors), as for xwb_copy_envs.
+ *   plans_dev   int8 [n][n_plans][horizon] in device memory: action ids as xwb_step takes them.  XWB_ACTION_SKIP ends a plan (the
+ *               padding of ragged plans); any other id outside [0, num_actions) ends it too and adds one to the error counter.
+ *               Neither counts as a step.  (Read in 16- or 4-byte pieces when horizon is a multiple and the buffer aligned.)
+ * Row i starts from the state the NEXT xwb_step would act on for env envs[i] -- never a look-ahead snapshot or a pre-generated
+ * episode -- and applies xwb_step(actions, act_rep)'s rule action by action: the move (act_rep repeats; headings and turns in
+ * egocentric mode), the task's reward, time limit (dims^2 * max_steps_factor; a curriculum env's own dims) and event, max_steps,
+ * and the game-over code, which outside lang_acquisition ignores the task's events.  A plan stops after the first step that
+ * leaves a non-zero game-over code.  Outputs, [n][n_plans] each; any may be NULL, not all:
+ *   steps_dev   int32: steps executed, 0 .. horizon
+ *   code_dev    uint8: the game-over code after the last executed step (XWB_ALIVE: the plan ran out, or executed nothing)
+ *   return_dev  float32: ret = 0, g = 1; per executed step, in order: ret = ret + g * r_t; g = g * gamma -- r_t the float the step
+ *               would store in the reward array, every product and sum rounded to float32 on its own (the library is built
+ *               with -ffp-contract=off; no fused multiply-add), so a caller who repeats the recurrence in float32 gets the bits
+ *   last_dev    int32: (heading << 16) | (y * max_dim + x) of the agent after the last executed step -- the index [heading][cell]
+ *               into xwb_xw_expert's field: heading 0 under full observation (one plane), 0 +x, 1 +y, 2 -x, 3 -y in egocentric mode
+ * An env whose game-over code is set and that has not been reset (between xwb_step and xwb_reset_done) reports steps 0, that
+ * code, return 0 and its current node for every plan -- the expert's rule for such envs; after xwb_step_autoreset, which keeps
+ * the codes but has reset the envs, the new episodes are evaluated.
+ * Supported: one XWorld3DNav* group (confs/navigation2d.json, confs/nav_target.json), full observation and every egocentric
+ * radius, curriculum batches, every max_dim up to 16, either RNG mode, either task mode.
+ * XWB_ERR_ARG, and nothing is launched: a game other than XWorld2D; two task groups, or a group of the 2-D-native tasks (their
+ * idle stage draws at step time); plans_dev NULL; n_plans, horizon or act_rep < 1; n < 0 with an index list; all four outputs
+ * NULL; gamma not finite; an index list or a 4-byte output that is not 4-byte aligned.  n = 0 does nothing.  A poisoned batch:
+ * XWB_ERR_STATE.
+ * One kernel launch on `stream`, behind the verbs queued there; no allocation, no copy, no host synchronisation, no work on the
+ * internal queue.  It changes nothing but the error counter: the next xwb_step's path (xwb_step_path), shadow_breaks, the
+ * snapshot and pre-generation flags, xwb_save_state blobs and every result of a rollout are the same with and without calls in
+ * between; the performance counters, the curriculum windows, headings and XWB_RNG_MINSTD engines are not touched.  (Between
+ * xwb_step and its xwb_reset_done one event orders the internal queue's LATER work -- the reset's map generator -- behind the
+ * kernel, because the finished envs' nodes are read.)
+ * Cost: the kernel is latency- and ALU-bound -- n * n_plans * horizon bytes in, a few words per plan out; one wavefront per
+ * workgroup, one lane per plan, 64 / n_plans envs per workgroup when n_plans is small (docs/kernels.md, docs/measurements.md). */
+int xwb_xw_evaluate_plans(xwb_sim *sim, const int32_t *envs_dev, int32_t n, const int8_t *plans_dev, int32_t n_plans,
+                          int32_t horizon, int32_t act_rep, float gamma, float *return_dev, int32_t *steps_dev,
+                          uint8_t *code_dev, int32_t *last_dev, void *stream);
+
 /* (test and measurement hooks -- xwb_debug_stall_handoff, xwb_profile_begin / _end / _stop -- are not part of this boundary:
  * include/xwb_testing.h, version node XWB_TESTING of csrc/libxwb.map) */
 

@@ -577,6 +577,66 @@ class BatchedSimulator:
         self._copy_lists = (d, s)                              # (keeps lists copied from the host alive until the next call)
         return self
 
+    def evaluate_plans(self, plans, gamma=1.0, act_rep=1, envs=None, last=False, out=None, stream=None):
+        """xwb_xw_evaluate_plans: what step(actions, act_rep) would pay for each of K action sequences of length H per env, from
+        the state the next step() acts on, in one kernel launch on `stream` and without writing any of the batch's state (the
+        read-only counterpart of "copy_envs into child slots, step, reset_done").  One XWorld3DNav* task group only (XwbError for
+        two groups or the 2-D-native tasks).
+        plans: a contiguous int8 CUDA tensor [n, K, H] of action ids; -1 (XWB_ACTION_SKIP) ends a plan (padding of ragged plans),
+        any other id outside [0, num_actions) ends it too and shows up in check_errors().  envs: None (row i = env i, n =
+        num_envs) or n env indices -- an int32 CUDA tensor used as it is (an index outside the batch: steps -1, last -1, one count
+        in check_errors()), or anything torch.as_tensor takes, copied to the device.
+        Returns (returns, steps, codes) or, with last=True, (returns, steps, codes, last): CUDA tensors [n, K] -- float32
+        discounted returns (ret = ret + g * r_t; g = g * gamma in float32, step order), int32 steps executed (a plan stops after
+        the first step that leaves a game-over code), uint8 game-over code after the last executed step, int32 (heading << 16) |
+        cell of the agent after it (the index into expert(field=True)'s field).  A finished env that awaits its reset_done():
+        steps 0, its code, return 0.  The tensors are allocated on the first call with a shape and reused by the later ones;
+        out=(returns, steps, codes[, last]) -- contiguous tensors of those types and shape, or None for an output that is not
+        wanted (returned as None; at least one must be given) -- uses the caller's."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not isinstance(plans, torch.Tensor) or plans.dtype != torch.int8 or plans.dim() != 3 or plans.device != dev \
+                or not plans.is_contiguous():
+            raise ValueError("plans: a contiguous int8 tensor [n, K, H] on %s" % dev)
+        n, k, h = (int(v) for v in plans.shape)
+        idx = None
+        if envs is None:
+            if n != self.num_envs:
+                raise ValueError("plans: %d rows for %d envs (pass envs= for a subset)" % (n, self.num_envs))
+        else:
+            idx = self._env_list("envs", envs, dev).to(dev)
+            if int(idx.numel()) != n:
+                raise ValueError("evaluate_plans: %d env indices for %d rows of plans" % (idx.numel(), n))
+        names = ("returns", "steps", "codes", "last")
+        dtypes = (torch.float32, torch.int32, torch.uint8, torch.int32)
+        if out is None:
+            own = getattr(self, "_plan_bufs", None)
+            if own is None:
+                own = self._plan_bufs = {}
+            bufs = []
+            for name, dt in zip(names[:4 if last else 3], dtypes):
+                if (name, n, k) not in own:
+                    own[(name, n, k)] = torch.empty((n, k), dtype=dt, device=dev)
+                bufs.append(own[(name, n, k)])
+        else:
+            bufs = list(out)
+            if len(bufs) != (4 if last else 3):
+                raise ValueError("out: (returns, steps, codes%s), None for an output that is not wanted" % (", last" if last else ""))
+            for t, name, dt in zip(bufs, names, dtypes):
+                if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != dev or tuple(t.shape) != (n, k)
+                                      or not t.is_contiguous()):
+                    raise ValueError("out: %s must be a contiguous %s tensor of shape %s on %s" % (name, dt, (n, k), dev))
+        ptrs = [C.c_void_p(t.data_ptr()) if t is not None else None for t in bufs] + [None] * (4 - len(bufs))
+        if idx is not None and n == 0:                         # (no rows: nothing to evaluate; a NULL list would mean every env)
+            return tuple(bufs)
+        if k * h == 0:                                         # (an empty tensor has no address: the library still checks the rest)
+            plans = torch.zeros(1, dtype=torch.int8, device=dev)
+        lib.check(self.L.xwb_xw_evaluate_plans(self.h, C.c_void_p(idx.data_ptr()) if idx is not None else None, n,
+                                               C.c_void_p(plans.data_ptr()), k, h, int(act_rep), float(gamma), *ptrs,
+                                               self._stream(stream)))
+        self._plan_idx = idx                                   # (keeps a list copied from the host alive until the next call)
+        return tuple(bufs)
+
     def env_state(self, env=0, stream=None):
         st = lib.XwbEnvState()
         lib.check(self.L.xwb_get_env_state(self.h, int(env), self._stream(stream), C.byref(st)))

@@ -14,6 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libxwb.so")
 SOURCES = ["kernels_simple.hip", "kernels_xworld.hip", "kernels_xworld_reset.hip", "kernels_xworld_ego.hip", "kernels_xworld_ego_span.hip",
            "kernels_xworld_view.hip", "kernels_xworld_expert.hip", "kernels_xworld_symbolic.hip", "kernels_copy_envs.hip",
+           "kernels_xworld_plans.hip",
            "xwb_create.hip", "xwb_ego_tables.hip", "xwb_verbs.hip", "xwb_getters.hip", "xwb_checkpoint.hip", "xwb_comm.hip",
            "xwb_sentence_ids.hip"]
 # every object depends on every header: the headers source_fingerprint hashes

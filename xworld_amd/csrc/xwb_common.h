@@ -399,6 +399,11 @@ hipError_t launch_xw_view(const XwParams &p, int src, const int32_t *envs, int n
 // ignore_done: the done codes are those of envs already reset
 hipError_t launch_xw_expert(const XwParams &p, int32_t *actions, int32_t *dist, uint16_t *field, int no_path_action, bool ignore_done,
                             hipStream_t s);
+// plan evaluation (kernels_xworld_plans.hip): for row i = env envs[i] (NULL: env i; an index outside the batch: steps -1 and one
+// count in err_count) and each of its n_plans plans (int8 [n][n_plans][horizon]) what the step rule of the batch's one XWorld3DNav*
+// group would pay, [n][n_plans] per nullable output.  Reads the live state; ignore_done as for the expert
+hipError_t launch_xw_plans(const XwParams &p, const int32_t *envs, int n, const int8_t *plans, int n_plans, int horizon, int act_rep,
+                           float gamma, float *ret, int32_t *steps, uint8_t *code, int32_t *last, bool ignore_done, hipStream_t s);
 // symbolic observations (kernels_xworld_symbolic.hip): int16 [n][3][S][S], S = max_dim or visible_radius -- what each square of
 // every env's newest frame shows (planes XWB_SYM_PLANE_*).  src: PACK_SRC_*, full observation
 hipError_t launch_xw_symbolic(const XwParams &p, int src, int16_t *out, hipStream_t s);

@@ -966,6 +966,46 @@ int xwb_xw_expert(xwb_sim *s, int32_t *actions_dev, int32_t *dist_dev, uint16_t 
     return XWB_OK;
 }
 
+int xwb_xw_evaluate_plans(xwb_sim *s, const int32_t *envs_dev, int32_t n, const int8_t *plans_dev, int32_t n_plans, int32_t horizon,
+                          int32_t act_rep, float gamma, float *return_dev, int32_t *steps_dev, uint8_t *code_dev, int32_t *last_dev,
+                          void *stream) {
+    if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
+    XWB_ON_DEVICE(s);
+    XWB_LIVE(s);
+    if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_ARG, "not an xworld batch");
+    const XwParams &xw = s->xw;
+    if (xw.n_tasks2 > 0)
+        return fail(XWB_ERR_ARG, "the batch has two task groups: plans are evaluated for ONE XWorld3DNav* group (a second group's stage "
+                                 "runs in every step and may draw)");
+    if (xw.group2d)
+        return fail(XWB_ERR_ARG, "the batch's group holds the 2-D-native tasks: their idle stage draws a task and a target at step "
+                                 "time, so a plan's outcome is not a function of its action ids alone");
+    if (!plans_dev) return fail(XWB_ERR_ARG, "plans_dev is NULL");
+    if (n_plans < 1 || horizon < 1 || act_rep < 1) return fail(XWB_ERR_ARG, "n_plans, horizon and act_rep must be >= 1");
+    if (envs_dev && n < 0) return fail(XWB_ERR_ARG, "n must be >= 0");
+    if (!return_dev && !steps_dev && !code_dev && !last_dev) return fail(XWB_ERR_ARG, "all four outputs are NULL");
+    if (!std::isfinite(gamma)) return fail(XWB_ERR_ARG, "gamma must be finite");
+    if ((reinterpret_cast<uintptr_t>(envs_dev) | reinterpret_cast<uintptr_t>(return_dev) | reinterpret_cast<uintptr_t>(steps_dev) |
+         reinterpret_cast<uintptr_t>(last_dev)) & 3u)
+        return fail(XWB_ERR_ARG, "envs_dev, return_dev, steps_dev and last_dev must be 4-byte aligned");
+    if (xw.max_dim > XW_MAX_DIM) return fail(XWB_ERR_ARG, "max_dim exceeds the kernel's grid staging");
+    if (!envs_dev) n = s->n;
+    if (n == 0) return XWB_OK;
+    hipStream_t st = as_stream(stream);
+    // Reads the live state the next xwb_step reads, as xwb_xw_expert does (see there: only kernels on `stream` write it between
+    // verbs).  One difference: an env the last xwb_step finished reports its node (`last`), i.e. its agent cell and heading are
+    // read, and on the classic path a later xwb_reset_done regenerates those on the internal queue.  While such envs exist
+    // (step_open) one event orders that queue's LATER work behind this kernel, as xwb_xw_render_view does for egocentric batches.
+    HIP_TRY(launch_xw_plans(xw_params(s), envs_dev, n, plans_dev, n_plans, horizon, act_rep, gamma, return_dev, steps_dev, code_dev,
+                            last_dev, s->autoreset_done, st));
+    if (s->step_open) {
+        if (!s->ev_view) HIP_TRY(hipEventCreateWithFlags(&s->ev_view, hipEventDisableTiming | hipEventDisableSystemFence));   // (made on first use)
+        HIP_TRY(hipEventRecord(s->ev_view, st));
+        HIP_TRY(hipStreamWaitEvent(s->side, s->ev_view, 0));
+    }
+    return XWB_OK;
+}
+
 int xwb_xw_symbolic_dims(const xwb_sim *s, size_t *planes, size_t *rows, size_t *cols) {
     if (!s) return fail(XWB_ERR_ARG, "sim is NULL");
     if (s->cfg.game != XWB_XWORLD2D) return fail(XWB_ERR_ARG, "not an xworld batch");

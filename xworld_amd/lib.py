@@ -171,6 +171,7 @@ _SIGS = [
     ("xwb_xw_symbolic_dims", C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("xwb_xw_symbolic", C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     ("xwb_copy_envs", C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
+    ("xwb_xw_evaluate_plans", C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     ("xwb_run", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     ("xwb_last_error", C.c_char_p, []),
     ("xwb_version", C.c_char_p, []),
