@@ -40,6 +40,9 @@ CASES = {
     "factor1": _case(ec.NAV2D, *_M5, prefix=20, limit=True, max_steps_factor=1),
     "max_steps12": _case(ec.NAV2D, *_N7, prefix=5, limit=True, max_steps=12),
     "act_rep2": _case(ec.NAV2D, *_N7, act_rep=2),
+    # egocentric repeats: a turn is applied on every repeat and the contact of an earlier repeat is kept; the prefix is played by
+    # the step kernels with act_rep 2, so every later number depends on the headings they stored
+    "ego3_act_rep2": _case(ec.NAV2D, *_N7, act_rep=2, visible_radius=3),
     # outside lang_acquisition the code ignores the task's events: an episode ends on max_steps alone (every env on the same step,
     # so one case cannot hold both plans that cross it and plans that do not: max_steps12 is the case that crosses), and a plan
     # that wins is paid + 1 and goes on.  One group, so exclusive scheduling has nothing to choose

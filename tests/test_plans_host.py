@@ -39,7 +39,7 @@ def test_symbol_is_declared_exported_and_typed():
     assert re.search(r"global:[^;]*\bxwb_\*", nodes["XWB_1"]) and NAME not in nodes["XWB_TESTING"]
     from xworld_amd import build
     assert "kernels_xworld_plans.hip" in build.SOURCES
-    assert os.path.exists(os.path.join(build.CSRC, "kernels_xworld_plans.hip")) and os.path.exists(os.path.join(build.CSRC, "xw_plan_rule.h"))
+    assert os.path.exists(os.path.join(build.CSRC, "kernels_xworld_plans.hip")) and os.path.exists(os.path.join(build.CSRC, "xw_step_rule.h"))
 
 
 def test_abi_version_matches_the_binding():

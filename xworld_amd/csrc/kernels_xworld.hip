@@ -23,7 +23,7 @@
 #include "xwb_common.h"
 #include <cstdlib>
 #include <cstring>
-#include "xw_device.h"
+#include "xw_step_rule.h"
 
 namespace xwb {
 
@@ -65,21 +65,18 @@ __device__ __forceinline__ void wave_append2(bool flag, int value, uint32_t valu
 
 // What one teach() call hands a task group's stage (Task::py_stage pushes the same into the Python env)
 struct StepCtx {
-    int e, D, ax, ay, steps, hit, hit_cell, ddx, ddy, vx, vy;
-    bool success;
-    int level;
+    Move m;
+    int e, steps, level;
     bool hit_is_goal;           // the item bumped into is a goal (icon type 0)
 };
 
 // One task group's stage in one Teacher::teach call: group G's task FSM (ts_in / tsteps_in -> ts_out / tsteps_out), the
 // reward it adds to the teacher buffer and the event it leaves there (every py_stage overwrites it).
 template <int G>
-__device__ __forceinline__ void teach_group(const XwParams &p, const StepCtx &c, int ts, int tsteps_in,
+__device__ __forceinline__ void teach_group(const XwParams &p, const StepRule &rule, const StepCtx &c, int ts, int tsteps_in,
                                             double &rew, int &event, int &ts_out, int &tsteps_out, bool &defer_idle) {
     defer_idle = false;
-    const int e = c.e, D = c.D, ax = c.ax, ay = c.ay, steps = c.steps, hit = c.hit, hit_cell = c.hit_cell;
-    const int ddx = c.ddx, ddy = c.ddy, vx = c.vx, vy = c.vy, ld_level = c.level;
-    const bool success = c.success;
+    const int e = c.e, D = p.max_dim;
     const bool group2d = G ? p.group2d_2 != 0 : p.group2d != 0;
     int target = task_target(ts), kind = task_kind(ts);
     int stage = task_stage(ts);
@@ -94,7 +91,7 @@ __device__ __forceinline__ void teach_group(const XwParams &p, const StepCtx &c,
         if (stage == STAGE_IDLE) {
             Stream s2;
             s2.init(p.seed, p.env_gid0 + (uint32_t)e, p.episode[e], 2u);
-            s2.blk = (uint32_t)steps;
+            s2.blk = (uint32_t)c.steps;
             const int k2 = task_at<G>(p, sample_task<G>(p, s2, e));
             kind = k2;
             idle_2d(kind, p.cand2d[e], p.goal_cells + (size_t)e * XW_MAX_GOALS,
@@ -102,14 +99,14 @@ __device__ __forceinline__ void teach_group(const XwParams &p, const StepCtx &c,
             rew = 0.0;
         } else if (stage == STAGE_NAV) {
             rew = -0.1;                             // time_penalty
-            if (!success) rew += -0.2;              // failed_action_penalty
+            if (!c.m.success) rew += -0.2;          // failed_action_penalty
             tsteps += 1;
             if (p.task_mode == 1 && tsteps >= D * D / 2) {           // one_channel: h*w / 2 (max dims)
                 tsteps = 0;
                 record = 0;                         // _record_failure
                 timeup = true;
                 stage = STAGE_IDLE;                 // "S -> timeup"
-            } else if (ay * D + ax == target) {     // agent.loc == self.target
+            } else if (c.m.ay * D + c.m.ax == target) {   // agent.loc == self.target
                 tsteps = 0;
                 record = 1;                         // _record_success
                 event = EV_CORRECT; rew += 1.0;
@@ -123,38 +120,8 @@ __device__ __forceinline__ void teach_group(const XwParams &p, const StepCtx &c,
         // event -- the stage itself runs in xw_idle3d_kernel, right behind this kernel, over the envs listed here.
         defer_idle = true;
     } else if (stage == STAGE_NAV) {
-        rew = -0.01;                                // time_penalty
-        tsteps += 1;
-        const int dim = p.curriculum != 0 ? 3 + ld_level : p.dim;             // env.get_dims()
-        if (tsteps >= dim * dim * p.max_steps_factor) {
-            event = EV_TIMEUP;
-            record = 0;
-            timeup = true;
-            stage = STAGE_TERMINAL;
-        } else if (hit != 0 && ddx == vx && ddy == vy && c.hit_is_goal) {
-            // _reach_object: id in collisions and |theta| < pi/4, i.e. the goal was bumped into along the
-            // heading: MOVE_DOWN under full observation (yaw stays 1.5707963), MOVE_FORWARD in egocentric mode.
-            // Target / Near / Avoid: the reached goal is in self.target (cell bit 15, set by the idle stage)
-            // -> correct, else wrong.  Between: any reached goal is wrong.  Direction: (direction(g, referent,
-            // agent.yaw), near) is evaluated now, the yaw being the current heading.
-            bool good = kind != TASK_BETWEEN && (hit & CELL_TARGET_BIT);
-            if (kind == TASK_DIRECTION && target >= 0) {        // (a replayed map may carry the bits only)
-                const int rc = target & 0xff, word = (target >> 8) & 7;
-                const int v2x = rc % D - hit_cell % D, v2y = rc / D - hit_cell / D;
-                const int cs = vx * v2x + vy * v2y, sn = vy * v2x - vx * v2y;
-                const int dirw = cs > 0 ? DIR_FRONT : (cs < 0 ? DIR_BEHIND : (sn > 0 ? DIR_RIGHT : DIR_LEFT));
-                good = v2x * v2x + v2y * v2y == 1 && dirw == word;
-            }
-            if (good) { event = EV_CORRECT; rew += 1.0; }
-            else { event = EV_WRONG; rew += -1.0; }
-            record = good ? 1 : 0;                  // _successful_goal / _failed_goal
-            stage = STAGE_TERMINAL;
-        } else if (kind == TASK_BETWEEN && ay * D + ax == target) {
-            // XWorld3DNavTargetBetween.navigation_reward: dist(agent, middle) < threshold / 2
-            event = EV_CORRECT; rew += 1.0;
-            record = 1;
-            stage = STAGE_TERMINAL;
-        }
+        const NavStage s = nav_stage_3d(rule, c.m, c.hit_is_goal, ts, tsteps, c.level);
+        rew = s.rew; event = s.event; stage = s.stage; tsteps = s.tsteps; record = s.record; timeup = s.timeup;
     }
     if (record >= 0 && p.curriculum != 0) usage_push(p.cur_usage + ((size_t)e * 9 + kind) * XW_USAGE_BYTES, record);
     if (record >= 0) {
@@ -176,11 +143,6 @@ struct StepIn {
     uint32_t ep;
     uint4 gc;                                              // the env's goal-slot table (goal_cells)
 };
-// ... and what the move leaves for the teacher
-struct Move {
-    int ax, ay, hit, hit_cell, ddx, ddy, vx, vy, dir;
-    bool success;
-};
 
 __device__ __forceinline__ void xw_load_step_in(const XwParams &p, int e, StepIn &in) {
     in.axy = p.agent_xy[e]; in.steps = p.num_steps[e]; in.ts = p.task_state[e]; in.tsteps = p.task_steps[e];
@@ -193,73 +155,24 @@ __device__ __forceinline__ void xw_load_step_in(const XwParams &p, int e, StepIn
     in.gc = reinterpret_cast<const uint4 *>(p.goal_cells)[e];
 }
 
-// XAgent::act x act_rep on the env's grid.  `lg` = a private copy of the grid the move reads and keeps current (LDS);
-// `g` = the live grid, whose two changed cells are stored as well when it is given.
-__device__ __forceinline__ Move xw_move(const XwParams &p, int e, int a, int axy, int dir_in, uint16_t *lg, uint16_t *g) {
-    const int D = p.max_dim;
-    Move m;
-    m.ax = axy & 0xffff; m.ay = axy >> 16;
-    m.dir = dir_in;
-    const uint16_t agent_code = lg[m.ay * D + m.ax];
-    m.ddx = a == 2 ? -1 : (a == 3 ? 1 : 0);             // MOVE_LEFT / MOVE_RIGHT
-    m.ddy = a == 0 ? -1 : (a == 1 ? 1 : 0);             // MOVE_UP / MOVE_DOWN
-    m.vx = 0; m.vy = 1;                                  // heading: entities keep yaw 1.5707963 (+y) under full observation
-    m.hit = 0; m.hit_cell = 0;
-    m.success = false;
-    for (int i = 0; i < p.act_rep; ++i) {
-        if (p.visible_radius) {
-            // XAgent::act, xitem.cpp:103-155: MOVE_FORWARD, MOVE_BACKWARD, MOVE_LEFT_FPV, MOVE_RIGHT_FPV relative to
-            // the heading; TURN_LEFT / TURN_RIGHT change the yaw and "move" onto the agent's own cell, which
-            // XMap::move_item refuses (xmap.cpp:76-101): a turn is an unsuccessful action without contacts
-            int dir = m.dir;
-            if (a == 4) dir = (dir + 3) & 3;
-            else if (a == 5) dir = (dir + 1) & 3;
-            m.dir = dir;
-            p.agent_dir[e] = (uint8_t)dir;
-            m.vx = dir == 0 ? 1 : (dir == 2 ? -1 : 0);
-            m.vy = dir == 1 ? 1 : (dir == 3 ? -1 : 0);
-            const int lx = m.vy, ly = -m.vx;            // MOVE_LEFT_FPV: right->up, down->right, left->down, up->left
-            m.ddx = a == 0 ? m.vx : (a == 1 ? -m.vx : (a == 2 ? lx : (a == 3 ? -lx : 0)));
-            m.ddy = a == 0 ? m.vy : (a == 1 ? -m.vy : (a == 2 ? ly : (a == 3 ? -ly : 0)));
-        }
-        const int tx = m.ax + m.ddx, ty = m.ay + m.ddy;
-        m.success = false;
-        if (p.visible_radius && a >= 4) continue;       // a turn
-        if (tx >= 0 && ty >= 0 && tx < D && ty < D) {
-            const int code = lg[ty * D + tx];
-            if (code == 0) {                             // XMap::move_item: empty cell -> move
-                lg[m.ay * D + m.ax] = 0;
-                lg[ty * D + tx] = agent_code;
-                if (g) { g[m.ay * D + m.ax] = 0; g[ty * D + tx] = agent_code; }
-                m.ax = tx; m.ay = ty;
-                m.success = true;
-            } else {
-                m.hit = code;                            // contact_list -> "collision:<id>" event
-                m.hit_cell = ty * D + tx;
-            }
-        }
+// The cells xw_move sees in a step: `lg` = the wavefront's private copy of the env's grid (LDS), which the move reads and keeps
+// current; `g` = the live grid, whose two changed cells are stored as well.
+struct StepCells {
+    uint16_t *lg, *g;
+    uint16_t agent_code;
+    __device__ __forceinline__ int code(int cell) const { return lg[cell]; }
+    __device__ __forceinline__ void moved(int from, int to) {
+        lg[from] = 0; lg[to] = agent_code;
+        g[from] = 0; g[to] = agent_code;
     }
-    return m;
-}
+};
 
 // Teacher::teach + XWorldSimulator::game_over for one env after its move, and the stores of everything the step leaves
 // behind except the grid.
-__device__ __forceinline__ void xw_teach_store(const XwParams &p, int e, const StepIn &in, const Move &m, bool &is_done, bool &idle3d) {
-    const int D = p.max_dim;
+__device__ __forceinline__ void xw_teach_store(const XwParams &p, const StepRule &rule, int e, const StepIn &in, const Move &m, bool &is_done,
+                                               bool &idle3d) {
     const int steps = in.steps + 1;                       // GameSimulator::take_actions: once per call
-    const int hit = m.hit, hit_cell = m.hit_cell;
-    // "the item bumped into is a goal": its cell is in the env's goal-slot table (0xff = no goal; cell 255 exists on a
-    // 16 x 16 map only, where the icon's type is looked up instead)
-    bool hit_is_goal = false;
-    if (hit != 0) {
-        if (D > 15) hit_is_goal = p.icon_type[(hit & CELL_ICON_MASK) - 1] == 0;
-        else {
-            const uint32_t rep = (uint32_t)hit_cell * 0x01010101u;
-            auto has = [&](uint32_t w) { const uint32_t x = w ^ rep; return ((x - 0x01010101u) & ~x & 0x80808080u) != 0u; };
-            hit_is_goal = has(in.gc.x) || has(in.gc.y) || has(in.gc.z) || has(in.gc.w);
-        }
-    }
-    StepCtx cx{e, D, m.ax, m.ay, steps, hit, hit_cell, m.ddx, m.ddy, m.vx, m.vy, m.success, in.level, hit_is_goal};
+    StepCtx cx{m, e, steps, in.level, m.hit != 0 && hit_is_goal(rule, m.hit, m.hit_cell, in.gc)};
     const int ld_ts = in.ts, ld_tsteps = in.tsteps, ld_ts2 = in.ts2, ld_tsteps2 = in.tsteps2;
     double rew = 0.0;
     int event = EV_NONE;
@@ -276,11 +189,11 @@ __device__ __forceinline__ void xw_teach_store(const XwParams &p, int e, const S
         double r0;
         bool defer;
         if (pick == 0) {
-            teach_group<0>(p, cx, ld_ts, ld_tsteps, r0, event, ts_new, tsteps_new, defer);
+            teach_group<0>(p, rule, cx, ld_ts, ld_tsteps, r0, event, ts_new, tsteps_new, defer);
             p.task_state[e] = ts_new;
             p.task_steps[e] = tsteps_new;
         } else {
-            teach_group<1>(p, cx, ld_ts2, ld_tsteps2, r0, event, ts_new, tsteps_new, defer);
+            teach_group<1>(p, rule, cx, ld_ts2, ld_tsteps2, r0, event, ts_new, tsteps_new, defer);
             p.task_state2[e] = ts_new;
             p.task_steps2[e] = tsteps_new;
         }
@@ -301,25 +214,23 @@ __device__ __forceinline__ void xw_teach_store(const XwParams &p, int e, const S
         {
             int ts_new, tsteps_new;
             double r0;
-            teach_group<0>(p, cx, ld_ts, ld_tsteps, r0, event, ts_new, tsteps_new, defer);
+            teach_group<0>(p, rule, cx, ld_ts, ld_tsteps, r0, event, ts_new, tsteps_new, defer);
             rew = 0.0 + r0;                             // add_teacher_reward on a cleared buffer
             p.task_state[e] = ts_new;
             p.task_steps[e] = tsteps_new;
         }
         if (p.n_tasks2 > 0) {
-            cx.hit = 0;                                 // game_events_ was consumed by the first group's py_stage
+            cx.m.hit = 0;                               // game_events_ was consumed by the first group's py_stage
             int ts_new, tsteps_new;
             double r1;
-            teach_group<1>(p, cx, ld_ts2, ld_tsteps2, r1, event, ts_new, tsteps_new, defer);
+            teach_group<1>(p, rule, cx, ld_ts2, ld_tsteps2, r1, event, ts_new, tsteps_new, defer);
             rew += r1;
             p.task_state2[e] = ts_new;
             p.task_steps2[e] = tsteps_new;
         }
     }
-    float r = 0.0f;                                 // SimulatorInterface::take_actions
-    r += 0.0f;                                      // XWorldSimulator::take_action returns 0
-    r = (float)((double)r + rew);                   // r += teacher_->give_reward() (double)
-    const int code = done_code(p, steps, event);
+    const float r = step_reward(rew);
+    const int code = done_code(rule, steps, event);
     p.agent_xy[e] = m.ax | (m.ay << 16);
     p.num_steps[e] = steps;
     p.success[e] = m.success ? 1 : 0;
@@ -380,8 +291,13 @@ __device__ __forceinline__ void xw_step_body(const XwParams &p, const int blk, c
             atomicAdd(p.err_count, 1);
         } else {
             // the live grid gets the move's two cells; they are read from (and kept current in) the wavefront's LDS copy
-            const Move m = xw_move(p, e, a, in.axy, in.dir, s_grid + lane * cells_all, p.grid + (size_t)e * cells_all);
-            xw_teach_store(p, e, in, m, is_done, idle3d);
+            const StepRule rule = step_rule(p);
+            uint16_t *lg = s_grid + lane * cells_all;
+            const int ax = in.axy & 0xffff, ay = in.axy >> 16;
+            StepCells cells{lg, p.grid + (size_t)e * cells_all, lg[ay * p.max_dim + ax]};
+            const Move m = xw_move(rule, a, p.act_rep, ax, ay, in.dir, cells);
+            if (p.visible_radius) p.agent_dir[e] = (uint8_t)m.dir;
+            xw_teach_store(p, rule, e, in, m, is_done, idle3d);
             axy_new = m.ax | (m.ay << 16);
         }
     }

@@ -2,7 +2,8 @@
 // the fewest xwb_step calls (act_rep 1) after which its XWorld3DNav* task group records "correct_goal", the first action of
 // such a sequence, and on request the same number for every cell and heading the agent could stand on.
 //
-// "Success" is what teach_group (kernels_xworld.hip) rewards in STAGE_NAV, read off the code, not re-derived:
+// "Success" is what nav_stage_3d (xw_step_rule.h) rewards, read off the code, not re-derived; "is a goal" and the direction word
+// are that header's hit_is_goal and direction_word:
 //   Target / Near / Avoid   a move along the heading into a goal whose cell code carries the target bit
 //   Direction               ... into a goal one cell from the referent, the direction word holding for the heading of the bump
 //                           (target < 0, a replayed map: the target-bit rule)
@@ -25,7 +26,7 @@
 // The field leaves as 2-byte stores, one per reached node, over a 0xFFFF fill the wavefront stores first with 16-byte stores.
 // Every loop is bounded: the scan by max_dim^2, the search by headings * max_dim^2 levels, a level's stores by 64 per word.
 #include "xwb_common.h"
-#include "xw_device.h"
+#include "xw_step_rule.h"
 
 namespace xwb {
 
@@ -170,6 +171,7 @@ __global__ __launch_bounds__(64) void xw_expert_kernel(XwParams p, ExpertArgs x)
     // the env's boards: cells inside the map, occupied cells, goals, goals that carry the target bit
     B inb = b_zero<W>(), occ = b_zero<W>(), goal = b_zero<W>(), tgt = b_zero<W>();
     if (search) {
+        const StepRule rule = step_rule(p);
         const uint16_t *lg = s_grid + lane * pitch;
 #pragma unroll
         for (int i = 0; i < W; ++i) {
@@ -184,16 +186,7 @@ __global__ __launch_bounds__(64) void xw_expert_kernel(XwParams p, ExpertArgs x)
                     m_in |= bit;
                     if (code == 0) continue;
                     m_occ |= bit;
-                    // "the item is a goal": xw_teach_store's rule (the env's goal-slot table; the icon's type on a 16 x 16 map)
-                    bool is_goal;
-                    if (D > 15) {
-                        const uint32_t ic = (code & CELL_ICON_MASK) - 1u;
-                        is_goal = ic < (uint32_t)p.n_icons && p.icon_type[ic] == 0;
-                    } else {
-                        const uint32_t rep = (uint32_t)cell * 0x01010101u;
-                        auto has = [&](uint32_t w) { const uint32_t v = w ^ rep; return ((v - 0x01010101u) & ~v & 0x80808080u) != 0u; };
-                        is_goal = has(gc.x) || has(gc.y) || has(gc.z) || has(gc.w);
-                    }
+                    const bool is_goal = hit_is_goal(rule, (int)code, cell, gc);
                     if (is_goal) m_goal |= bit;
                     if (is_goal && (code & CELL_TARGET_BIT)) m_tgt |= bit;
                 }
@@ -222,9 +215,7 @@ __global__ __launch_bounds__(64) void xw_expert_kernel(XwParams p, ExpertArgs x)
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             const int v2x = dir_dx(o), v2y = dir_dy(o), gx = rx - v2x, gy = ry - v2y;
-            const int cs = vx * v2x + vy * v2y, sn = vy * v2x - vx * v2y;
-            const int dirw = cs > 0 ? DIR_FRONT : (cs < 0 ? DIR_BEHIND : (sn > 0 ? DIR_RIGHT : DIR_LEFT));
-            if (dirw == word && (unsigned)gx < (unsigned)D && (unsigned)gy < (unsigned)D) r = b_or(r, b_bit<W>((gy << SH) + gx));
+            if (direction_word(vx, vy, v2x, v2y) == word && (unsigned)gx < (unsigned)D && (unsigned)gy < (unsigned)D) r = b_or(r, b_bit<W>((gy << SH) + gx));
         }
         return b_and(r, goal);
     };

@@ -1,10 +1,11 @@
 // kernels_xworld_plans.hip -- xwb_xw_evaluate_plans (include/xwb.h): what the step rule would pay for K action sequences of
 // length H per env, read off the env's current state without writing a byte of it.
 //
-// The rule is xw_plan_rule.h's plan_step: a pure restatement of xw_move / teach_group / done_code for a batch whose one task
-// group holds XWorld3DNav* tasks.  A plan is a chain of H dependent steps of a few dozen integer instructions each, on an LDS
-// grid and ~10 registers: the kernel is bound by that chain and by the one memory round trip in front of it, not by bandwidth
-// (it reads n * K * H plan bytes and one grid per env, and writes up to 13 bytes per plan).
+// The rule is xw_step_rule.h's, the one the step kernels run: plan_step below composes its move, goal test, XWorld3DNav* stage,
+// reward conversion and game-over code for a batch whose one task group holds XWorld3DNav* tasks.  A plan is a chain of H
+// dependent steps of a few dozen integer instructions each, on an LDS grid and ~10 registers: the kernel is bound by that chain
+// and by the one memory round trip in front of it, not by bandwidth (it reads n * K * H plan bytes and one grid per env, and
+// writes up to 13 bytes per plan).
 //
 // Shape: one wavefront per workgroup, as the step and expert kernels.  The 64 lanes are cut into slots of L = min(64, K rounded
 // up to a power of two) lanes; a slot owns one row i (one env) and its lanes take that row's plans, one each -- 64 / L rows per
@@ -17,14 +18,46 @@
 // Plan bytes: a lane reads its plan front to back in pieces of 16, 4 or 1 bytes -- the widest that divides H and the buffer's
 // alignment --, the next piece requested when the current one is begun.
 #include "xwb_common.h"
-#include "xw_plan_rule.h"
+#include "xw_step_rule.h"
 
 namespace xwb {
 
 namespace {
 
+// Under an XWorld3DNav* group a step draws no random number and moves nothing but the agent, so a plan reads the env's grid as it
+// found it, with one exception: the agent's ORIGINAL cell, which is empty once the agent has left it (and which the agent itself
+// can re-enter).  Everything a step changes beyond that is a handful of registers (PlanState).
+// What a plan reads of its env and never changes; the cells xw_move sees
+struct PlanEnv {
+    const uint16_t *lg;          // the env's max_dim^2 cell codes (target bits included), as the plan's first step finds them
+    int cell0;                   // the agent's cell in lg: reads as empty
+    int level;                   // curriculum level (0 without curriculum)
+    uint4 gc;                    // the env's goal-slot table (goal_cells)
+    __device__ __forceinline__ int code(int cell) const { return cell == cell0 ? 0 : (int)lg[cell]; }
+    __device__ __forceinline__ void moved(int, int) const {}
+};
+
+// what a step changes
+struct PlanState {
+    int ax, ay, dir;             // the agent's cell and heading (dir: XwParams::agent_dir; stays 1 under full observation)
+    int ts, tsteps, steps;       // task_state, task_steps, num_steps
+};
+
+// One xwb_step call for one env: action a (legal: 0 .. 3, 0 .. 5 in egocentric mode) x act_rep.  Updates st; *reward = the float
+// the step stores in reward[e]; returns the game-over code it stores in done[e].
+__device__ __forceinline__ int plan_step(const StepRule &p, const PlanEnv &v, PlanState &st, int a, int act_rep, float *reward) {
+    const Move m = xw_move(p, a, act_rep, st.ax, st.ay, st.dir, v);
+    const NavStage s = nav_stage_3d(p, m, m.hit != 0 && hit_is_goal(p, m.hit, m.hit_cell, v.gc), st.ts, st.tsteps, v.level);
+    *reward = step_reward(s.rew);
+    st.ax = m.ax; st.ay = m.ay; st.dir = m.dir;
+    st.ts = pack_task(task_target(st.ts), s.stage, s.event, task_kind(st.ts));
+    st.tsteps = s.tsteps;
+    st.steps += 1;                                          // GameSimulator::take_actions: once per call
+    return done_code(p, st.steps, s.event);
+}
+
 struct PlanArgs {
-    PlanRule rule;
+    StepRule rule;
     int n_envs;                  // num_envs of the batch
     int n, n_plans, horizon, act_rep;
     int ignore_done;             // the last verb was xwb_step_autoreset: the envs whose codes are set have been reset already
@@ -62,7 +95,7 @@ template <int W>
 __global__ __launch_bounds__(64) void xw_plans_kernel(PlanArgs x, int lanes_per_row) {
     typedef typename PlanPiece<W>::T Piece;
     extern __shared__ uint32_t s_grid_dw[];                // [rows of this workgroup][pitch_dw]
-    const PlanRule &p = x.rule;
+    const StepRule &p = x.rule;
     const int lane = threadIdx.x;
     const int L = lanes_per_row, rows = 64 / L;
     const int D = p.max_dim, cells = D * D, pitch = plan_pitch_dw(D);
@@ -166,8 +199,7 @@ __global__ __launch_bounds__(64) void xw_plans_kernel(PlanArgs x, int lanes_per_
 hipError_t launch_xw_plans(const XwParams &q, const int32_t *envs, int n, const int8_t *plans, int n_plans, int horizon, int act_rep,
                            float gamma, float *ret, int32_t *steps, uint8_t *code, int32_t *last, bool ignore_done, hipStream_t s) {
     PlanArgs x{};
-    x.rule = PlanRule{q.max_dim, q.dim, q.max_steps, q.max_steps_factor, q.task_mode, q.visible_radius, q.n_icons,
-                      q.curriculum != 0 ? 1 : 0, q.icon_type};
+    x.rule = step_rule(q);
     x.n_envs = q.n; x.n = n; x.n_plans = n_plans; x.horizon = horizon; x.act_rep = act_rep;
     x.ignore_done = ignore_done ? 1 : 0;
     x.gamma = gamma;

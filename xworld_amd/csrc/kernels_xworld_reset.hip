@@ -18,7 +18,7 @@
 // instruction fetches miss all the way to L2 while render_all saturates the memory system
 #define XWB_PHILOX_ATTR __noinline__
 #include "xwb_common.h"
-#include "xw_device.h"
+#include "xw_step_rule.h"
 #include "../../include/xwb_trig.h"
 
 namespace xwb {
@@ -387,8 +387,7 @@ __device__ __forceinline__ void xw_idle_stage_3d(const XwParams &p, int e, Strea
                     // __compute_triple_direction(target, referent, e): view = e -> target, v2 = target -> referent
                     const int v1x = tl % D - ec % D, v1y = tl / D - ec / D;
                     const int v2x = rl % D - tl % D, v2y = rl / D - tl / D;
-                    const int c = v1x * v2x + v1y * v2y, sn = v1y * v2x - v1x * v2y;
-                    direction = c > 0 ? DIR_FRONT : (c < 0 ? DIR_BEHIND : (sn > 0 ? DIR_RIGHT : DIR_LEFT));
+                    direction = direction_word(v1x, v1y, v2x, v2y);
                     seed = ec; inclusive = true;                     // _propagate_agent([e], inclusive=True)
                 }
             }
@@ -489,9 +488,7 @@ __device__ __forceinline__ void xw_idle_stage_3d(const XwParams &p, int e, Strea
                     const int c = L.gcell[L.at(i)];
                     const int v2x = rl % D - c % D, v2y = rl / D - c / D;
                     if (v2x * v2x + v2y * v2y != 1) continue;         // dist == 0 -> False; dist > 1.001 -> far
-                    const int cs = hx * v2x + hy * v2y, sn = hy * v2x - hx * v2y;
-                    const int dir = cs > 0 ? DIR_FRONT : (cs < 0 ? DIR_BEHIND : (sn > 0 ? DIR_RIGHT : DIR_LEFT));
-                    if (dir == direction) target_bits |= 1u << i;
+                    if (direction_word(hx, hy, v2x, v2y) == direction) target_bits |= 1u << i;
                 }
                 tf = ((rl / D + off) * MD + (rl % D + off)) | (direction << 8);
             }
@@ -792,7 +789,7 @@ __device__ void xw_reset_env(const XwParams &p, const IconTables &T, const LaneL
     p.num_steps[e] = 0;
     p.fresh[e] = 2;                                       // render: init_screen (zero the older context frames)
     atomicAdd(p.perf + 36, 1ull);                         // games reset
-    if (!keep_done) p.done[e] = (uint8_t)done_code(p, 0, EV_NONE);
+    if (!keep_done) p.done[e] = (uint8_t)done_code(step_rule(p), 0, EV_NONE);
     RP_T(4);
 }
 

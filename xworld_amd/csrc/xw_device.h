@@ -131,18 +131,6 @@ __device__ __forceinline__ void xw_wait_epoch_lane(const uint32_t *epoch_slot, u
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
 }
 
-__device__ __forceinline__ int done_code(const XwParams &p, int num_steps, int event) {
-    // AgentSpecificSimulator::game_over = GameSimulator::game_over | XWorldSimulator::game_over
-    int code = (p.max_steps > 0 && num_steps >= p.max_steps) ? MAX_STEP : ALIVE;
-    if (p.task_mode == 0) {       // lang_acquisition, xworld_simulator.cpp:166-177
-        if (event == EV_CORRECT) code |= SUCCESS;
-        else if (event == EV_WRONG) code |= DEAD;
-        else if (event == EV_TIMEUP) code |= MAX_STEP;
-    }
-    return code;
-}
-
-
 // TaskGroup::run_stage's sample_task (teaching_task.cpp:204-213): util::get_rand_ind, or for the "weighted" schedule
 // util::simple_importance_sampling (simulator_util.cpp:57-86): a float uniform in [0, float(total)), first task whose
 // accumulated weight is >= it.  One draw either way.
@@ -230,21 +218,6 @@ __device__ inline int curriculum_configure(const XwParams &p, int e) {
     if (usage >= p.curriculum && level < 5) level++;
     p.cur_level[e] = (uint8_t)level;
     return level;
-}
-
-// The move XAgent::act x act_rep (xitem.cpp:89-101) + XMap::move_item (xmap.cpp:76-101) makes on the cell codes `lg` of one env
-// under full observation: the agent's code goes up to act_rep cells along action a (MOVE_UP, MOVE_DOWN, MOVE_LEFT, MOVE_RIGHT)
-// while the next cell is inside the map and empty.  Returns the agent's new cell; *from = its old one (equal: no move).
-__device__ __forceinline__ int xw_predict_move(const uint16_t *lg, int D, int axy, int a, int act_rep, int *from) {
-    int ax = axy & 0xffff, ay = axy >> 16;
-    *from = ay * D + ax;
-    const int ddx = a == 2 ? -1 : (a == 3 ? 1 : 0), ddy = a == 0 ? -1 : (a == 1 ? 1 : 0);
-    for (int i = 0; i < act_rep; ++i) {
-        const int tx = ax + ddx, ty = ay + ddy;
-        if (tx < 0 || ty < 0 || tx >= D || ty >= D || lg[ty * D + tx] != 0) break;      // (blocked once = blocked for good)
-        ax = tx; ay = ty;
-    }
-    return ay * D + ax;
 }
 
 // ---- shared by the render kernels ----
