@@ -4,6 +4,8 @@ import os
 import numpy as np
 import pytest
 
+from _blob import _blob_layout, _walk
+
 pytestmark = pytest.mark.gpu
 
 CONF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "xworld_amd", "confs")
@@ -142,47 +144,6 @@ def test_refused_load_leaves_the_batch_alone():
     assert a.check_errors() == b.check_errors() == 0
     a.close()
     b.close()
-
-
-XW_USAGE_BYTES, XW_MAX_GOALS = 32, 16
-
-
-def _blob_layout(n, frames, cells=0, simple_game=False, simple_race=False, minstd=False, groups=1, exclusive=False, ego=False,
-                 curriculum=False):
-    """The lengths of a version-4 blob's arrays, in order (n envs, `frames` bytes of frames per env or None, cells = max_dim^2)."""
-    a = [4 * n, 4 * n, 4 * n, 4 * n, n, n, 4, 4 * ((n + 255) // 256)]        # actions, num_steps, episode, reward, done, success, errors, reset counts
-    if simple_game:
-        a += [4 * n, n]
-    if simple_race:
-        a += [4 * n, 4 * n, 4 * n]
-    if minstd:
-        a += [4 * n]
-    if cells:
-        a += [2 * n * cells, 4 * n, 4 * n, 4 * n]                            # grid, agent, task steps, task state
-        if groups == 2:
-            a += [4 * n, 4 * n]
-            if exclusive:
-                a += [n]
-        a += [4 * n, 4, n, 320, XW_MAX_GOALS * n, 4 * n, n, 4 * n]           # done list, its counter, fresh, perf, goal cells, cand2d, heading, names
-        if ego:
-            a += [XW_MAX_GOALS * 6 * 8 * n]                                  # goal warps: 768 n
-        if curriculum:
-            a += [n, 4 * n, 9 * n * XW_USAGE_BYTES]
-    if frames is not None:
-        a += [n * frames]
-    return a
-
-
-def _walk(blob):
-    """(n_arrays of the 56-byte header, the uint64 length in front of each array), the blob consumed to its last byte"""
-    raw = blob.tobytes()
-    assert raw[:8] == b"XWBSTATE" and int.from_bytes(raw[8:12], "little") == 4
-    n_arrays, at, lengths = int.from_bytes(raw[24:28], "little"), 56, []
-    while at < len(raw):
-        lengths.append(int.from_bytes(raw[at:at + 8], "little"))
-        at += 8 + lengths[-1]
-    assert at == len(raw)
-    return n_arrays, lengths
 
 
 TWO_GROUPS = {"xwd_conf_path": os.path.join(CONF, "nav_two_groups.json"), "max_steps": 50, "max_dim": 7, "num_blocks": 16}

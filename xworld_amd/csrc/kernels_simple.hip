@@ -173,13 +173,23 @@ __global__ __launch_bounds__(256) void sg_kernel(SgParams p) {
     store_reset_count(p.reset_partial, n_reset);
 }
 
+// init_screen (simulator.cpp:110-113) for chunk j of one env's frames: zeros, then the frame that shows `pos` last -- what a
+// reset leaves, and what xwb_load_state draws when the blob carries no frames
+template <int G>
+__device__ __forceinline__ void sg_write_first_frame(const SgParams &p, int env, int j, int pos) {
+    using chunk_t = typename ChunkT<G>::type;
+    const int A = p.array_size, cpf = A / G, ctx = p.context;
+    chunk_t *frame0 = reinterpret_cast<chunk_t *>(p.obs + ((size_t)env * ctx) * A) + j;
+    for (int f = 0; f + 1 < ctx; ++f) frame0[(size_t)f * cpf] = zero_chunk<G>();
+    frame0[(size_t)(ctx - 1) * cpf] = sg_onehot_chunk<G>(pos - j * G);
+}
+
 // reset_game for the envs a mode selects (all / game over / mask), as its own kernel: a reset needs nothing of an env's old
 // state but its episode counter, so the lanes load `done` (or the mask) and `episode` in ONE round trip, and lanes that
 // do not reset touch nothing else -- the generic kernel in a reset mode loaded and wrote back the whole state of every
 // env (the reset_done pass of the example loop then cost more than the step it follows).
 template <int G>
 __global__ __launch_bounds__(256) void sg_reset_kernel(SgParams p) {
-    using chunk_t = typename ChunkT<G>::type;
     __shared__ uint8_t s_reset[256];
     const int tid = threadIdx.x;
     const int e = blockIdx.x * 256 + tid;
@@ -200,16 +210,13 @@ __global__ __launch_bounds__(256) void sg_reset_kernel(SgParams p) {
         p.pos[e] = pos; p.flags[e] = 0; p.num_steps[e] = 0; p.episode[e] = episode + 1;
         p.done[e] = (uint8_t)(sg_over(pos, A) ? SUCCESS : ALIVE);     // over at once for array_size <= 2; num_steps_ == 0 < max_steps
     }
-    // init_screen (simulator.cpp:110-113): zeros, then the first frame last
-    const int cpf = A / G, ctx = p.context;
+    const int cpf = A / G;
     const int base_env = blockIdx.x * 256;
     const int n_here = min(256, p.n - base_env);
     for (int i = tid; i < n_here * cpf; i += 256) {
         const int le = i / cpf, j = i - le * cpf;
         if (!s_reset[le]) continue;
-        chunk_t *frame0 = reinterpret_cast<chunk_t *>(p.obs + ((size_t)(base_env + le) * ctx) * A) + j;
-        for (int f = 0; f + 1 < ctx; ++f) frame0[(size_t)f * cpf] = zero_chunk<G>();
-        frame0[(size_t)(ctx - 1) * cpf] = sg_onehot_chunk<G>(pos - j * G);
+        sg_write_first_frame<G>(p, base_env + le, j, pos);
     }
     store_reset_count(p.reset_partial, do_reset ? 1 : 0);
 }
@@ -224,6 +231,27 @@ hipError_t launch_simple_game(const SgParams &p, hipStream_t s) {
     else if (p.array_size % 4 == 0) SG_LAUNCH(4);
     else SG_LAUNCH(1);
 #undef SG_LAUNCH
+    return hipGetLastError();
+}
+
+// The newest frame of every env drawn from its state, the older context frames black: what xwb_load_state leaves when the blob
+// carries no frames (a frame is a function of `pos` alone, for a finished env too).  Writes nothing but frames.
+template <int G>
+__global__ __launch_bounds__(256) void sg_draw_kernel(SgParams p) {
+    const int cpf = p.array_size / G;
+    const int base_env = blockIdx.x * 256;
+    const int n_here = min(256, p.n - base_env);
+    for (int i = threadIdx.x; i < n_here * cpf; i += 256) {
+        const int le = i / cpf, j = i - le * cpf;
+        sg_write_first_frame<G>(p, base_env + le, j, p.pos[base_env + le]);
+    }
+}
+
+hipError_t launch_simple_game_draw(const SgParams &p, hipStream_t s) {
+    dim3 grid((p.n + 255) / 256), block(256);
+    if (p.array_size % 16 == 0) hipLaunchKernelGGL((sg_draw_kernel<16>), grid, block, 0, s, p);
+    else if (p.array_size % 4 == 0) hipLaunchKernelGGL((sg_draw_kernel<4>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((sg_draw_kernel<1>), grid, block, 0, s, p);
     return hipGetLastError();
 }
 
@@ -440,6 +468,15 @@ __global__ __launch_bounds__(256) void race_kernel(RaceParams p) {
     store_reset_count(p.reset_partial, L.n_reset);
 }
 
+// init_screen for env e: [env][context][4] floats; older frames zero, the frame of car `c` last (see sg_write_first_frame)
+__device__ __forceinline__ void race_write_first_frame(const RaceParams &p, int e, const RaceCar &c) {
+    double sa, ca;
+    xwb_sincos((double)c.angle, &sa, &ca);
+    float4 *frames = reinterpret_cast<float4 *>(p.obs) + (size_t)e * p.context;
+    for (int f = 0; f + 1 < p.context; ++f) frames[f] = make_float4(0, 0, 0, 0);
+    frames[p.context - 1] = race_screen(p, c, ca, sa);
+}
+
 // reset_game for the envs a mode selects, as its own kernel (see sg_reset_kernel): `done` / mask and `episode` in one round
 // trip; lanes that do not reset leave at once, the others write the new car, counters, code and first frame.
 __global__ __launch_bounds__(256) void race_reset_kernel(RaceParams p) {
@@ -460,12 +497,7 @@ __global__ __launch_bounds__(256) void race_reset_kernel(RaceParams p) {
         race_reset(p, c, p.env_gid0 + (uint32_t)e, episode, p.minstd ? p.minstd + e : nullptr);
         p.x[e] = c.x; p.y[e] = c.y; p.angle[e] = c.angle; p.num_steps[e] = 0; p.episode[e] = episode;
         p.done[e] = (uint8_t)(race_oob(p, c.x, c.y) ? DEAD : ALIVE);        // game_over() right after the reset
-        double sa, ca;
-        xwb_sincos((double)c.angle, &sa, &ca);
-        // init_screen: [env][context][4] floats; older frames zero, the first frame last
-        float4 *frames = reinterpret_cast<float4 *>(p.obs) + (size_t)e * p.context;
-        for (int f = 0; f + 1 < p.context; ++f) frames[f] = make_float4(0, 0, 0, 0);
-        frames[p.context - 1] = race_screen(p, c, ca, sa);
+        race_write_first_frame(p, e, c);
     }
     store_reset_count(p.reset_partial, do_reset ? 1 : 0);
 }
@@ -475,6 +507,21 @@ hipError_t launch_simple_race(const RaceParams &p, hipStream_t s) {
     if (p.mode != MODE_STEP) hipLaunchKernelGGL(race_reset_kernel, grid, block, 0, s, p);
     else if (!p.actions && p.context == 1 && !p.minstd) hipLaunchKernelGGL(race_kernel<true>, grid, block, 0, s, p);
     else hipLaunchKernelGGL(race_kernel<false>, grid, block, 0, s, p);
+    return hipGetLastError();
+}
+
+// The newest frame of every env drawn from its car, the older context frames black (see sg_draw_kernel): the step and reset
+// kernels draw a frame from cos / sin of the very angle they store, so this is the frame they drew.
+__global__ __launch_bounds__(256) void race_draw_kernel(RaceParams p) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= p.n) return;
+    RaceCar c;
+    c.x = p.x[e]; c.y = p.y[e]; c.angle = p.angle[e];
+    race_write_first_frame(p, e, c);
+}
+
+hipError_t launch_simple_race_draw(const RaceParams &p, hipStream_t s) {
+    hipLaunchKernelGGL(race_draw_kernel, dim3((p.n + 255) / 256), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

@@ -150,6 +150,10 @@ int xwb_load_state(xwb_sim *s, const uint8_t *in_host, size_t bytes) {
             HIP_TRY(launch_xw_render(p, RENDER_ALL, nullptr));
         }
     }
+    else if (!h.include_obs) {                          // the simple games: a frame is a function of the restored state
+        if (s->cfg.game == XWB_SIMPLE_GAME) HIP_TRY(launch_simple_game_draw(sg_params(s), nullptr));
+        else HIP_TRY(launch_simple_race_draw(race_params(s), nullptr));
+    }
     HIP_TRY(hipDeviceSynchronize());
     return XWB_OK;
 }

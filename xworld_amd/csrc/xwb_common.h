@@ -156,6 +156,7 @@ struct SgParams {
                                 // nearly every wavefront holds an env that just finished)
 };
 hipError_t launch_simple_game(const SgParams &p, hipStream_t s);
+hipError_t launch_simple_game_draw(const SgParams &p, hipStream_t s);   // frames from the state alone (xwb_load_state without frames)
 
 // ------------------------------------------------------------ SimpleRace ---
 struct RaceParams {
@@ -184,6 +185,7 @@ struct RaceParams {
     uint32_t *minstd;           // nullable: XWB_RNG_MINSTD, one libstdc++ minstd_rand0 state per env (include/xwb_minstd.h)
 };
 hipError_t launch_simple_race(const RaceParams &p, hipStream_t s);
+hipError_t launch_simple_race_draw(const RaceParams &p, hipStream_t s);
 
 // -------------------------------------------------------------- XWorld2D ---
 constexpr int XW_MAX_DIM = 16;
