@@ -145,6 +145,11 @@ EXCL_CASES = {
     "zero_weights": (T2, T3, [0, 0], {}),                   # conf without "weight" keys: the sort never swaps
     "near+color": (T3[1:2], T2[2:3], [1, 3], {}),
     "walls": (T2, T3[:1] + T3[4:], [1, 1], {"map": "XWorldWalls"}),
+    # boards past 64 and past 128 cells: the two- and four-word masks of the reset kernel and of xw_idle3d_kernel
+    "nav9": (T3, T2, [1, 1], {"max_dim": 9, "num_blocks": 20}),
+    "nav12": (T2, T3, [1, 1], {"max_dim": 12, "num_blocks": 30}),
+    "walls9": (T2, T3[:1] + T3[4:], [1, 1], {"map": "XWorldWalls", "max_dim": 9}),
+    "walls12": (T2, T3[:1] + T3[4:], [1, 1], {"map": "XWorldWalls", "max_dim": 12}),
     "ego": (T3, T2, [1, 1], {"visible_radius": 3}),
     "curriculum": (T2, T3, [2, 1], {"curriculum": 0.1, "max_dim": 8}),
     "minstd": (T3, T2, [1, 2], {"rng": "minstd", "simulator_seed": 7, "thread_base": 2}),

@@ -20,6 +20,8 @@ MAPS = {
     "nav8_dim5": (NAV, {"dim": 5, "num_goals": 2, "num_blocks": 6},
                   dict(map_kind=0, max_dim=8, dim=5, num_goals=2, num_blocks=6)),
     "walls7": (WALLS, {}, dict(map_kind=1, max_dim=7, dim=7, num_goals=12, num_blocks=12)),
+    "walls9": (WALLS, {"max_dim": 9}, dict(map_kind=1, max_dim=9, dim=9, num_goals=12, num_blocks=12)),
+    "walls12": (WALLS, {"max_dim": 12}, dict(map_kind=1, max_dim=12, dim=12, num_goals=12, num_blocks=12)),
 }
 
 
